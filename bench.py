@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- optimisation steps/sec of the CLIP-guided hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c1|c3|c4]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c1|c3|c4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload (BASELINE.json configs[1], "C2"): 1280x720 FFT parameteriser, ViT-B/32, `--samples 200` with the CLI
@@ -9,6 +9,10 @@ defaults (-tf fast => 190 effective cuts, clip_fft.py:167-169), sim 'mix', Adam(
 synth -> sampler -> ViT fwd -> loss -> ViT input-grad -> sampler adjoint -> rfft2 adjoint -> [all-reduce] -> Adam.
 Synthetic data: seeded random ViT weights / target embedding (no checkpoint or network here).  N > 1 splits the cuts
 across ranks (strong scaling of the fixed 200-sample step) with one RCCL all-reduce of the spectrum gradient per step.
+
+A plain run sets up, warms up with W steps, times exactly K steps once and prints the line.  `--full` adds the measurements
+below (`legs`, `roofline`, `cpu_baseline`; null in a plain line) and times the block of K steps 3 times (`--reps`).
+`--dump-outputs DIR` writes the last timed step's loss and the parameters it left as DIR/<name>.npy (dump_outputs()).
 
 The ONE JSON line (rank 0) carries, besides the driver's fields:
   * `value` = the headline (`-tf fast`, per-step frame off);
@@ -65,7 +69,11 @@ def parse():
     p.add_argument('--split', action='store_true', help='the opt-in split-precision forward (patch-embedding and QKV GEMMs on hi + lo f16 activation pairs): ~5 %% slower; '
                                                        'on the stress-weight loss-curve ensemble it is statistically indistinguishable from the default (profiles/r06_precision_ensemble.txt)')
     p.add_argument('--f16', action='store_true', help='(the default since round 6; accepted for old command lines) f16 operands on every ViT GEMM')
-    p.add_argument('--reps', type=int, default=3, help='repetitions of the timed block of --steps steps (value = the median block)')
+    p.add_argument('--reps', type=int, default=None, help='repetitions of the timed block of --steps steps (value = the median block); default 1, with --full 3')
+    p.add_argument('--full', action='store_true', help='everything besides the headline: legs, roofline, cpu_baseline (each still subject to its --no-* switch), '
+                                                       'and 3 timed blocks by default; a plain run times exactly --steps steps once')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed step returns to its caller '
+                                                                        '(loss, updated parameters) as DIR/<name>.npy')
     p.add_argument('--vit-path', default=None, help='measurement switch: comma list of name=int pairs handed to the library\'s test hooks '
                                                     '(rs: aph_gemm_set_rs, fused: aph_vit_set_fused_max_rows, ws: aph_gemm_set_ws_min_tiles, stream16: aph_vit_set_grad_stream_f16)')
     p.add_argument('--grad-f16', default=None, type=int, choices=[0, 1], help='measurement switch: Engine(grad_f16=...) -- the patch gradient handed to the sampler adjoint as f16 (1) or f32 (0); default: the engine\'s')
@@ -73,6 +81,10 @@ def parse():
     if a.split and a.f16:
         p.error('--split and --f16 are mutually exclusive')
     a.f16 = not a.split
+    if a.reps is None:
+        a.reps = 3 if a.full else 1
+    if not a.full:          # a plain run measures the headline only
+        a.no_legs = a.no_roofline = a.no_cpu_baseline = True
     cfg = dict(CONFIGS[a.config])
     for k in ('size', 'samples', 'model', 'transform'):
         if getattr(a, k) is not None:
@@ -275,12 +287,12 @@ def irdwt_roofline(eng):
 
 
 def other_config_legs(names, steps=30, timeout_s=90):
-    """`python bench.py --config <name>` (no legs, no CPU baseline, no roofline pass) in a child process per configuration -> its value line, abridged"""
+    """`python bench.py --full --config <name>` (no legs, no CPU baseline, no roofline pass) in a child process per configuration -> its value line, abridged"""
     import subprocess
     out = {}
     for name in names:
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--config', name, '--steps', str(steps), '--warmup', '5', '--no-cpu-baseline', '--no-legs',
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--full', '--config', name, '--steps', str(steps), '--warmup', '5', '--no-cpu-baseline', '--no-legs',
                                 '--no-roofline'], capture_output=True, text=True, timeout=timeout_s)
             lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
             if r.returncode != 0 or not lines:
@@ -315,6 +327,29 @@ def precision_block(f16):
     except (OSError, KeyError, ValueError):
         out['ensemble'] = None
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20          # every file of --dump-outputs together
+DUMP_SAMPLE = 1 << 22              # elements kept of an output larger than that (fixed seed: the same positions in every run)
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: {name: tensor or ndarray} -> out_dir/<name>.npy (float32, float64 kept); an output of more than DUMP_SAMPLE elements is
+    written as out_dir/<name>_sample.npy, its elements at DUMP_SAMPLE sorted positions drawn from a fixed seed.  -> {file name: shape}"""
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+        if x.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_SAMPLE, replace=False))
+            x, name = x.reshape(-1)[idx], name + '_sample'
+        total += x.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit('bench.py --dump-outputs: the outputs exceed %d bytes' % DUMP_MAX_BYTES)
+        np.save(os.path.join(out_dir, name + '.npy'), x)
+        written[name + '.npy'] = list(x.shape)
+    return written
 
 
 def lib_sha():
@@ -601,6 +636,11 @@ def main():
     blocks = [timed(eng, eng_b, a.steps, a.warmup if r == 0 else 0) for r in range(max(a.reps, 1))]
     dt = sorted(blocks)[len(blocks) // 2]
     loss = eng.global_loss()
+    if a.dump_outputs:          # before anything below steps an engine again: the last timed step's loss and the parameters it left
+        last = eng_b if (eng_b is not None and a.steps - 1 >= dualmod and (a.steps - 1) % dualmod == 0) else eng
+        last_loss = loss if last is eng else last.global_loss()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, dict(loss=np.array([last_loss], dtype=np.float64), params=eng.params))
     # multi-rank sanity, outside the timed region: the communicator's own rank count, and the parameters bit-identical on every rank
     # after warm-up + K steps (a 64-bit hash of the bit patterns: every rank applied the same all-reduced gradient)
     ranks_seen, params_identical = 1, None

@@ -2,7 +2,9 @@
 argument handling and the reference's sample-count derating, parameter layouts, weight loading."""
 import os
 import re
+import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -254,6 +256,36 @@ def test_bench_traffic_summary_matching(tmp_path, monkeypatch):
     write('r04_pmc_hbm_traffic.json', lib_sha256='L' * 64)
     t, src, stale, match = bench.pmc_traffic('r*_pmc_hbm_traffic*.json')
     assert (os.path.basename(src), stale, match) == ('r04_pmc_hbm_traffic.json', False, 'library')
+
+
+def test_bench_plain_run_and_full(monkeypatch):
+    """a plain bench.py line times --steps steps once and measures nothing else; --full restores legs / roofline / cpu_baseline and 3 blocks"""
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '7'])
+    a = bench.parse()
+    assert (a.steps, a.reps, a.no_legs, a.no_roofline, a.no_cpu_baseline, a.dump_outputs) == (7, 1, True, True, True, None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-legs'])
+    a = bench.parse()
+    assert (a.reps, a.no_legs, a.no_roofline, a.no_cpu_baseline) == (3, True, False, False)
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, shapes kept; an output larger than DUMP_SAMPLE elements becomes the same fixed-seed
+    sample in every run; the total is capped"""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    arrays = dict(loss=np.array([0.25]), params=torch.ones(2, 3, dtype=torch.float16), big=big)
+    got = bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    assert got == {'loss.npy': [1], 'params.npy': [2, 3], 'big_sample.npy': [1000]}
+    loss, params, s = (np.load(str(tmp_path / 'a' / n)) for n in ('loss.npy', 'params.npy', 'big_sample.npy'))
+    assert loss.dtype == np.float64 and loss[0] == 0.25 and params.dtype == np.float32 and (params == 1).all()
+    assert s.dtype == np.float32 and (np.diff(s) > 0).all() and s.max() < 5000        # distinct elements of `big`, in order
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'big_sample.npy')), s)
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 4000)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'c'), arrays)
 
 
 def test_committed_traffic_summaries_match_sources():

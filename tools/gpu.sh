@@ -4,7 +4,7 @@
 #   gpurun --timeout 2400 -- 'bash tools/gpu.sh <tag> <stage> [<stage> ...]'
 # Everything lands in gpurun_out/<tag>_*; what is to be judged gets copied into profiles/ afterwards.  Stages:
 #   tests        pytest -m gpu -s (printed parity numbers)              smoke      __graft_entry__.smoke()
-#   bench        the default bench.py line (C2 headline, legs, cpu_baseline)    benchall   bench.py --config c1 | c3 | c4 | c5
+#   bench        bench.py --full (C2 headline, legs, roofline, cpu_baseline)     benchall   bench.py --full --config c1 | c3 | c4 | c5
 #   prof         rocprofv3 --kernel-trace --stats of C2 and C4 -> kernel_stats_c{2,4}.{csv,txt}
 #   calib        FETCH_SIZE / WRITE_SIZE calibration on known 1 GiB streams (tools/pmc/pmc_calib) -> pmc_calibration.json
 #   pmc          FETCH / WRITE passes over C2 and C4 -> profiles-ready <tag>[_c4]_pmc_hbm_traffic.{csv,json} (+ bench lines quoting them)
@@ -40,14 +40,14 @@ for STAGE in "$@"; do
     smoke)
       timeout 180 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1; tail -1 $O/${TAG}_smoke.log ;;
     bench)
-      timeout 600 python bench.py --steps 40 > $O/${TAG}_bench_c2.json 2>> $O/${TAG}_bench.err; summ $O/${TAG}_bench_c2.json ;;
+      timeout 600 python bench.py --full --steps 40 > $O/${TAG}_bench_c2.json 2>> $O/${TAG}_bench.err; summ $O/${TAG}_bench_c2.json ;;
     benchall)
-      for c in c1 c3 c4 c5; do timeout 300 python bench.py --config $c --steps 30 --no-cpu-baseline > $O/${TAG}_bench_$c.json 2>> $O/${TAG}_bench.err; done
+      for c in c1 c3 c4 c5; do timeout 300 python bench.py --full --config $c --steps 30 --no-cpu-baseline > $O/${TAG}_bench_$c.json 2>> $O/${TAG}_bench.err; done
       summ $O/${TAG}_bench_c1.json $O/${TAG}_bench_c3.json $O/${TAG}_bench_c4.json $O/${TAG}_bench_c5.json ;;
     prof)
       for c in c2 c4; do
         (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof_$c -- python $R/bench.py --config $c --steps 20 $NOX > $O/${TAG}_prof_$c.log 2>&1)
-        python tools/prof_summary.py $O/${TAG}_prof_$c 65 $O/${TAG}_kernel_stats_$c.csv 48 > $O/${TAG}_kernel_stats_$c.txt 2>&1
+        python tools/prof_summary.py $O/${TAG}_prof_$c 25 $O/${TAG}_kernel_stats_$c.csv 48 > $O/${TAG}_kernel_stats_$c.txt 2>&1
         find $O/${TAG}_prof_$c -name '*.db' -size +5M -delete 2>/dev/null
         head -30 $O/${TAG}_kernel_stats_$c.txt | cut -c1-220
       done ;;
@@ -67,8 +67,8 @@ for STAGE in "$@"; do
       python tools/pmc_traffic.py $O/${TAG}_pmc_fetch_c2 $O/${TAG}_pmc_write_c2 ${TAG} "bench.py --steps 3 --warmup 2 --reps 1 --no-graph (C2: 1280x720, ViT-B/32, 190 cuts, -tf fast)" $CAL > $O/${TAG}_pmc_traffic.txt 2>&1
       python tools/pmc_traffic.py $O/${TAG}_pmc_fetch_c4 $O/${TAG}_pmc_write_c4 ${TAG}_c4 "bench.py --config c4 --steps 3 --warmup 2 --reps 1 --no-graph (C4: 3840x2160 DWT db3, ViT-B/16, 95 cuts)" $CAL > $O/${TAG}_pmc_traffic_c4.txt 2>&1
       cp profiles/${TAG}_pmc_hbm_traffic.* profiles/${TAG}_c4_pmc_hbm_traffic.* $O/ 2>/dev/null
-      timeout 300 python bench.py --steps 40 --no-cpu-baseline --no-legs > $O/${TAG}_bench_c2_with_traffic.json 2>> $O/${TAG}_bench.err
-      timeout 300 python bench.py --config c4 --steps 30 --no-cpu-baseline --no-legs > $O/${TAG}_bench_c4_with_traffic.json 2>> $O/${TAG}_bench.err
+      timeout 300 python bench.py --full --steps 40 --no-cpu-baseline --no-legs > $O/${TAG}_bench_c2_with_traffic.json 2>> $O/${TAG}_bench.err
+      timeout 300 python bench.py --full --config c4 --steps 30 --no-cpu-baseline --no-legs > $O/${TAG}_bench_c4_with_traffic.json 2>> $O/${TAG}_bench.err
       find $O -name '*counter_collection.csv' -size +30M -delete 2>/dev/null
       summ $O/${TAG}_bench_c2_with_traffic.json $O/${TAG}_bench_c4_with_traffic.json
       tail -n 3 $O/${TAG}_pmc_traffic.txt; tail -n 3 $O/${TAG}_pmc_traffic_c4.txt ;;
@@ -82,7 +82,7 @@ for STAGE in "$@"; do
     ensemble)
       timeout 1500 python tools/loss_ensemble.py $O/${TAG}_precision_ensemble > $O/${TAG}_precision_ensemble.log 2>&1; tail -25 $O/${TAG}_precision_ensemble.log ;;
     mr2)
-      APH_BENCH_BACKEND=gloo timeout 400 python bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-legs > $O/${TAG}_mr_gloo2.json 2> $O/${TAG}_mr_gloo2.err
+      APH_BENCH_BACKEND=gloo timeout 400 python bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-legs > $O/${TAG}_mr_gloo2.json 2> $O/${TAG}_mr_gloo2.err
       echo "rc $?"; cut -c1-600 $O/${TAG}_mr_gloo2.json; tail -3 $O/${TAG}_mr_gloo2.err ;;
     mr2torchrun)
       # the driver's own launch line for N > 1 (torchrun), two ranks on this one GPU through gloo: the supervisors run under torchrun's agent
