@@ -17,7 +17,7 @@ import torch  # noqa: F401  (load order matters)
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libaphantasia_hip.so')
 
-APH_OUT_NCHW_RAW, APH_OUT_NCHW_NORM, APH_OUT_PATCH_F16, APH_GRAD_PATCH_F16, APH_OUT_PATCH_F16_HILO = 0, 1, 2, 3, 4
+APH_OUT_NCHW_RAW, APH_OUT_NCHW_NORM, APH_OUT_PATCH_F16, APH_GRAD_PATCH_F16, APH_OUT_PATCH_F16_HILO, APH_OUT_PATCH_F32 = 0, 1, 2, 3, 4, 5
 APH_AUG_STRIDE = 16
 SIM_TYPES = {'cossim': 0, 'cos': 0, None: 0, 'mix': 1, 'ang': 2, 'dot': 3}
 
@@ -57,6 +57,7 @@ _PROTOTYPES = {
     'aph_frame_affine': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_void_p]),
     'aph_patchify_f16': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_patchify_f16_hilo': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'aph_patchify_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_unpatchify_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     'aph_vit_create': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     'aph_vit_destroy': (c_int, [c_void_p]),
@@ -65,6 +66,9 @@ _PROTOTYPES = {
     'aph_vit_forward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'aph_vit_forward_hilo': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'aph_vit_enable_hilo': (c_int, [c_void_p]),
+    'aph_vit_enable_f32': (c_int, [c_void_p]),
+    'aph_vit_forward_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'aph_vit_backward_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p]),
     'aph_vit_backward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p]),
     'aph_vit_backward_h': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p]),
     'aph_vit_profile': (c_int, [c_void_p, c_int]),
@@ -80,6 +84,7 @@ _PROTOTYPES = {
     'aph_mfma_rate': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'aph_gemm_rs_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'aph_gemm_ws_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'aph_gemm_f32_test': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'aph_gemm_f16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_gemm_f16_ld': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     'aph_sim_loss': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

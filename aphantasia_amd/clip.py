@@ -24,7 +24,7 @@ class _Encode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, visual):
         S = x.shape[0]
-        patches = ops.patchify(x.contiguous().float(), visual.patch_size)
+        patches = ops.patchify(x.contiguous().float(), visual.patch_size, lib=visual.lib, f32=visual.exact)
         enc = visual._forward_patches(patches, S)
         ctx.visual, ctx.S = visual, S
         ctx.gen = visual._generation
@@ -39,31 +39,41 @@ class _Encode(torch.autograd.Function):
         if v._generation != ctx.gen:          # another forward ran since: rebuild this node's activations
             v._forward_patches(patches, ctx.S)
             ctx.gen = v._generation
-        gp = v.handle.backward((g.float() * LOSS_SCALE).contiguous(), ctx.S, out_scale=1.0 / LOSS_SCALE)
-        return ops.unpatchify(gp, ctx.S, ctx.shape[2], v.patch_size), None
+        # (exact mode keeps the power-of-two loss scale: multiplying by it and by its inverse is exact in fp32)
+        gp = v.handle.backward((g.float() * LOSS_SCALE).contiguous(), ctx.S, out_scale=1.0 / LOSS_SCALE, f32=v.exact)
+        return ops.unpatchify(gp, ctx.S, ctx.shape[2], v.patch_size, lib=v.lib), None
 
 
 class VisualTransformer:
     """Stands in for clip.model.VisionTransformer: `.input_resolution`, `.patch_size`, callable."""
 
-    def __init__(self, cfg, weights, max_batch=256, lib=None):
+    def __init__(self, cfg, weights, max_batch=256, lib=None, exact=False):
+        """exact: every forward / backward on the fp32 path (aph_vit_forward_f32 / aph_vit_backward_f32)"""
         self.lib = lib
+        self.exact = bool(exact)
         self.cfg = dict(cfg)
         self.input_resolution = cfg['input_resolution']
         self.patch_size = cfg['patch_size']
         self.output_dim = cfg['output_dim']
         self.weights = weights
         self.handle = ops.VitHandle(cfg, weights, max_batch, lib=lib)
+        if self.exact:
+            self.handle.enable_f32()
         self._generation = 0
 
     def ensure_batch(self, S):
         if S > self.handle.max_batch:
             self.handle = ops.VitHandle(self.cfg, self.weights, S, lib=self.lib)
+            if self.exact:
+                self.handle.enable_f32()
 
-    def _forward_patches(self, patches, S, out=None, hilo=False):
+    def _forward_patches(self, patches, S, out=None, hilo=False, f32=None):
         self.ensure_batch(S)
         self._generation += 1
-        return self.handle.forward(patches, S, out, hilo=hilo)
+        f32 = self.exact if f32 is None else f32
+        if f32:
+            self.handle.enable_f32()          # (a no-op once enabled: an Engine(exact=True) enables it before any capture)
+        return self.handle.forward(patches, S, out, hilo=hilo, f32=f32)
 
     def __call__(self, x):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.input_resolution or x.shape[3] != self.input_resolution:
@@ -72,9 +82,9 @@ class VisualTransformer:
 
 
 class CLIPModel:
-    def __init__(self, name, cfg, weights, full_state=None, max_batch=256, lib=None):
+    def __init__(self, name, cfg, weights, full_state=None, max_batch=256, lib=None, exact=False):
         self.name = name
-        self.visual = VisualTransformer(cfg, weights, max_batch, lib=lib)
+        self.visual = VisualTransformer(cfg, weights, max_batch, lib=lib, exact=exact)
         self._full_state = full_state
         self.synthetic = full_state is None
 
@@ -96,18 +106,19 @@ class CLIPModel:
         return self
 
 
-def load(name='ViT-B/32', device='cuda', jit=False, weights=None, seed=1, max_batch=256):
-    """-> (model, None).  weights: path to an OpenAI CLIP checkpoint; None = seeded synthetic weights."""
+def load(name='ViT-B/32', device='cuda', jit=False, weights=None, seed=1, max_batch=256, exact=False):
+    """-> (model, None).  weights: path to an OpenAI CLIP checkpoint; None = seeded synthetic weights.
+    exact: the fp32 ViT path (f32-input MFMA GEMMs, fp32 attention and activations) -- what the reference computes on the CPU."""
     if weights is not None:
         vis, cfg, full = load_openai_checkpoint(weights)
         want = visual_config(name)
         if (cfg['patch_size'], cfg['width'], cfg['layers']) != (want['patch_size'], want['width'], want['layers']):
             raise ValueError('%s does not hold a %s visual tower' % (weights, name))
-        return CLIPModel(name, cfg, vis, full, max_batch), None
+        return CLIPModel(name, cfg, vis, full, max_batch, exact=exact), None
     cfg = visual_config(name)
     warnings.warn('aphantasia_amd.clip.load(%r): no checkpoint given -> seeded SYNTHETIC weights (seed %d); '
                   'images will not be meaningful, use --clip-weights for real runs' % (name, seed))
-    return CLIPModel(name, cfg, synthetic_visual_weights(cfg, seed), None, max_batch), None
+    return CLIPModel(name, cfg, synthetic_visual_weights(cfg, seed), None, max_batch, exact=exact), None
 
 
 def text_embedding(model, text, device='cuda'):

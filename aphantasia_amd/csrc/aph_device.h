@@ -124,6 +124,36 @@ __device__ __forceinline__ f32x16 mfma_32x32x16_f16(half8 a, half8 b, f32x16 c) 
 #endif
 }
 
+// v_mfma_f32_32x32x2_f32:  D[32x32] += A[32x2] * B[2x32], f32 operands (the exact path, aph_vit_forward_f32)
+//   A operand: lane l holds A[i = l & 31][k = l >> 5];  B operand: lane l holds B[k = l >> 5][n = l & 31]
+//   C/D:       the 32x32 layout of mfma_32x32x16_f16 (dtype-independent on gfx950)
+// Numerics: bit-for-bit the k-ordered fmaf chain fma(a1, b1, fma(a0, b0, c)) -- what the interpreter computes.
+__device__ __forceinline__ f32x16 mfma_32x32x2_f32(float a, float b, f32x16 c) {
+#ifdef APH_EMU
+  struct Slot { float a, b; };
+  const int lane = emu::lane_id();
+  Slot s{a, b};
+  memcpy(emu::wave_slot(lane), &s, sizeof(s));
+  emu::wave_barrier();
+  const int n = lane & 31;
+  for (int r = 0; r < 16; ++r) {
+    const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    float acc = c[r];
+    for (int k = 0; k < 2; ++k) {
+      Slot sa, sb;
+      memcpy(&sa, emu::wave_slot(i + 32 * k), sizeof(Slot));
+      memcpy(&sb, emu::wave_slot(n + 32 * k), sizeof(Slot));
+      acc = fmaf(sa.a, sb.b, acc);
+    }
+    c[r] = acc;
+  }
+  emu::wave_barrier();
+  return c;
+#else
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+#endif
+}
+
 // global_load_lds_dwordx4: each lane copies 16 bytes from its own global address straight into LDS at
 // (wave-uniform base) + lane * 16 -- asynchronous, tracked by vmcnt, no VGPR staging.
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {

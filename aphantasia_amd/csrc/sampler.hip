@@ -77,6 +77,8 @@ __device__ __forceinline__ void emit(void* out, int s, int c, int i, int j, int 
     reinterpret_cast<float*>(out)[(((size_t)s * 3 + c) * size + i) * size + j] = v;
   } else if (OUT == APH_OUT_NCHW_NORM) {
     reinterpret_cast<float*>(out)[(((size_t)s * 3 + c) * size + i) * size + j] = (v - kClipMean[c]) / kClipStd[c];
+  } else if (OUT == APH_OUT_PATCH_F32) {
+    reinterpret_cast<float*>(out)[patch_index(s, c, i, j, size, patch)] = (v - kClipMean[c]) / kClipStd[c];
   } else {
     reinterpret_cast<half_t*>(out)[patch_index(s, c, i, j, size, patch)] = (half_t)((v - kClipMean[c]) / kClipStd[c]);
   }
@@ -141,6 +143,11 @@ __device__ __forceinline__ void emit3(void* out, int s, int i, int j, int size, 
     q[0] = (half_t)((v0 - kClipMean[0]) / kClipStd[0]);
     q[1] = (half_t)((v1 - kClipMean[1]) / kClipStd[1]);
     q[2] = (half_t)((v2 - kClipMean[2]) / kClipStd[2]);
+  } else if (OUT == APH_OUT_PATCH_F32) {
+    float* q = reinterpret_cast<float*>(out) + patch_index(s, 0, i, j, size, patch);
+    q[0] = (v0 - kClipMean[0]) / kClipStd[0];
+    q[1] = (v1 - kClipMean[1]) / kClipStd[1];
+    q[2] = (v2 - kClipMean[2]) / kClipStd[2];
   } else if (OUT == APH_OUT_PATCH_F16_HILO) {
     // rows [hi (Kp) | lo (Kp)]: hi = f16(x), lo = f16(x - hi) -- the A operand of the split-precision patch embedding (aph_vit_forward_hilo)
     const int kp = 3 * patch * patch;
@@ -1097,6 +1104,13 @@ __global__ void patchify_kernel(const float* __restrict__ x, half_t* __restrict_
     out[q + kp] = (half_t)(x[idx] - (float)h);
   }
 }
+__global__ void patchify_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int S, int R, int p) {
+  const size_t n = (size_t)S * 3 * R * R;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
+    const int j = idx % R, i = (idx / R) % R, c = (idx / ((size_t)R * R)) % 3, s = idx / ((size_t)3 * R * R);
+    out[patch_index(s, c, i, j, R, p)] = x[idx];
+  }
+}
 __global__ void unpatchify_kernel(const float* __restrict__ g, float* __restrict__ out, int S, int R, int p, float gscale) {
   const size_t n = (size_t)S * 3 * R * R;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
@@ -1114,6 +1128,7 @@ static Geom to_geom(const aph_sample_geom* g) { return Geom{g->H, g->W, g->Hp, g
 static int check_geom(const aph_sample_geom* g, int out_mode, const char* who, int max_mode = 2) {
   if (!g) return aph_fail(APH_ERR_ARG, "%s: null geometry", who);
   if (out_mode == APH_OUT_PATCH_F16_HILO && max_mode == 2) max_mode = APH_OUT_PATCH_F16_HILO;      // forward only: the split-precision patch rows
+  if (out_mode == APH_OUT_PATCH_F32) max_mode = APH_OUT_PATCH_F32;            // both ways: the exact path's fp32 patch rows / their gradient
   if (g->S < 1 || g->size < 1 || g->H < 1 || g->W < 1 || g->Hp < g->H || g->Wp < g->W)
     return aph_fail(APH_ERR_ARG, "%s: bad geometry S=%d size=%d H=%d W=%d Hp=%d Wp=%d", who, g->S, g->size, g->H, g->W, g->Hp, g->Wp);
   if (out_mode < 0 || out_mode > max_mode || (out_mode == APH_GRAD_PATCH_F16 && max_mode != APH_GRAD_PATCH_F16))
@@ -1277,6 +1292,7 @@ int aph_sample_fwd(const aph_sample_geom* gg, const float* rgb, const int32_t* t
     if (out_mode == APH_OUT_NCHW_RAW) launch_crop_resize<APH_OUT_NCHW_RAW>(rgb, (const int*)table, out, g, ws, st);
     else if (out_mode == APH_OUT_NCHW_NORM) launch_crop_resize<APH_OUT_NCHW_NORM>(rgb, (const int*)table, out, g, ws, st);
     else if (out_mode == APH_OUT_PATCH_F16) launch_crop_resize<APH_OUT_PATCH_F16>(rgb, (const int*)table, out, g, ws, st);
+    else if (out_mode == APH_OUT_PATCH_F32) launch_crop_resize<APH_OUT_PATCH_F32>(rgb, (const int*)table, out, g, ws, st);
     else launch_crop_resize<APH_OUT_PATCH_F16_HILO>(rgb, (const int*)table, out, g, ws, st);
     return aph_check_launch("aph_sample_fwd");
   }
@@ -1288,6 +1304,7 @@ int aph_sample_fwd(const aph_sample_geom* gg, const float* rgb, const int32_t* t
   if (out_mode == APH_OUT_NCHW_RAW) APH_LAUNCH(rotate_emit_kernel<APH_OUT_NCHW_RAW>, grid, block, 0, st, (const float*)A, (const float*)Bv, aug, out, n, g.patch);
   else if (out_mode == APH_OUT_NCHW_NORM) APH_LAUNCH(rotate_emit_kernel<APH_OUT_NCHW_NORM>, grid, block, 0, st, (const float*)A, (const float*)Bv, aug, out, n, g.patch);
   else if (out_mode == APH_OUT_PATCH_F16) APH_LAUNCH(rotate_emit_kernel<APH_OUT_PATCH_F16>, grid, block, 0, st, (const float*)A, (const float*)Bv, aug, out, n, g.patch);
+  else if (out_mode == APH_OUT_PATCH_F32) APH_LAUNCH(rotate_emit_kernel<APH_OUT_PATCH_F32>, grid, block, 0, st, (const float*)A, (const float*)Bv, aug, out, n, g.patch);
   else APH_LAUNCH(rotate_emit_kernel<APH_OUT_PATCH_F16_HILO>, grid, block, 0, st, (const float*)A, (const float*)Bv, aug, out, n, g.patch);
   return aph_check_launch("aph_sample_fwd");
   APH_CATCH
@@ -1297,6 +1314,7 @@ int aph_sample_bwd(const aph_sample_geom* gg, const void* gout, float gscale, co
                    void* ws, float* grgb, int out_mode, void* stream_) {
   APH_TRY
   if (int e = check_geom(gg, out_mode, "aph_sample_bwd", APH_GRAD_PATCH_F16)) return e;
+  if (out_mode == APH_OUT_PATCH_F32) out_mode = APH_OUT_PATCH_F16;      // the same gradient layout: f32 patch-major
   if (!gout || !table || !grgb || !ws) return aph_fail(APH_ERR_ARG, "aph_sample_bwd: null argument (the workspace of aph_sample_ws_bytes is required)");
   hipStream_t st = (hipStream_t)stream_;
   const Geom g = to_geom(gg);
@@ -1339,6 +1357,15 @@ int aph_patchify_f16_hilo(const float* x, int S, int R, int patch, void* out, vo
   if (!x || !out || S < 1 || R < 1 || patch < 1 || R % patch) return aph_fail(APH_ERR_ARG, "aph_patchify_f16_hilo: bad argument");
   APH_LAUNCH(patchify_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream_, x, (half_t*)out, S, R, patch, 1);
   return aph_check_launch("aph_patchify_f16_hilo");
+  APH_CATCH
+}
+
+// the exact path's operand: out f32 [S*(R/patch)^2, 3*patch*patch] (APH_OUT_PATCH_F32 layout), values unchanged
+int aph_patchify_f32(const float* x, int S, int R, int patch, float* out, void* stream_) {
+  APH_TRY
+  if (!x || !out || S < 1 || R < 1 || patch < 1 || R % patch) return aph_fail(APH_ERR_ARG, "aph_patchify_f32: bad argument");
+  APH_LAUNCH(patchify_f32_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream_, x, out, S, R, patch);
+  return aph_check_launch("aph_patchify_f32");
   APH_CATCH
 }
 

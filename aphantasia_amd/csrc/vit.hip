@@ -6,6 +6,7 @@
 // softmax statistics; the backward chain carries a static loss scale (applied by the caller to
 // d_enc, removed by `out_scale`) so fp16 gradient activations do not underflow.
 #include <cstring>
+#include <map>
 #include <string>
 #include <type_traits>
 
@@ -16,6 +17,8 @@
 #include "vit_gemm_rs.h"
 #include "vit_ops.h"
 #include "vit_attn.h"
+#include "vit_gemm_f32.h"
+#include "vit_attn_f32.h"
 #ifdef APH_EXPERIMENTS
 #include "vit_block.h"
 #endif
@@ -33,6 +36,10 @@ struct Layer {
   // per-layer activations kept for the backward
   float *x_in = nullptr, *x_mid = nullptr, *lse = nullptr;
   half_t *qkv = nullptr, *att = nullptr, *u = nullptr;
+  // exact path (aph_vit_enable_f32): fp32 weights [N, K] and their transposes, fp32 activations kept for the backward
+  float *w_qkv32 = nullptr, *w_qkvT32 = nullptr, *w_o32 = nullptr, *w_oT32 = nullptr;
+  float *w_fc1_32 = nullptr, *w_fc1T32 = nullptr, *w_fc2_32 = nullptr, *w_fc2T32 = nullptr;
+  float *qkv32 = nullptr, *dg32 = nullptr;
 };
 
 }  // namespace
@@ -53,6 +60,14 @@ struct aph_vit {
   size_t arena_bytes = 0;
   char* arena_hilo = nullptr;          // [r6] the K-repeated weight copies of the split-precision forward (w_patch2, w_qkv2): allocated by aph_vit_enable_hilo only
   size_t arena_hilo_bytes = 0;
+  // exact path (aph_vit_enable_f32): fp32 weights, the fp32 activation stash and gradient buffers, in an arena of their own
+  char* arena_f32 = nullptr;
+  size_t arena_f32_bytes = 0;
+  float *w_patch32 = nullptr, *w_patchT32 = nullptr;
+  float *h32 = nullptr, *g32 = nullptr, *att32 = nullptr, *datt32 = nullptr, *dqkv32 = nullptr, *delta32 = nullptr;
+  F32Space f32sp;                      // split-K partials of the fp32 class-row GEMMs
+  std::map<std::string, std::vector<float>> host32;      // host fp32 copies of the weight matrices (conv1.weight in the sampler's K order): the source of the fp32 arena
+  int last_fwd = 0;                    // precision of the last forward: 0 none, 1 f16 (aph_vit_forward / _hilo), 2 fp32 (aph_vit_forward_f32)
   int n_set = 0;
   // optional per-launch timing of the GEMM family (bench.py roofline): HIP event pairs on the launch stream
   bool prof_on = false;
@@ -87,6 +102,29 @@ int repeat_rows_k(half_t* dst, const half_t* src, size_t rows, size_t cols) {
   if (hipMemcpy2D(dst, 2 * w, src, w, w, rows, hipMemcpyDeviceToDevice) != hipSuccess) return -1;
   if (hipMemcpy2D(reinterpret_cast<char*>(dst) + w, 2 * w, src, w, w, rows, hipMemcpyDeviceToDevice) != hipSuccess) return -1;
   return 0;
+}
+
+// the exact path's arena (aph_vit_enable_f32): fp32 weights [N, K] and transposes, the fp32 stash (per block: qkv, dGELU/du), shared fp32
+// scratch (LayerNorm outputs / their gradients, GELU outputs / du, attention output / its gradient, dqkv, attention row dots) and the split-K
+// partials of the class-row GEMMs.  x_in / x_mid / lse / x0 / x_last / dx of the main arena are fp32 already and are shared with the f16 path.
+void carve_f32(aph_vit* v, char* base, size_t* total) {
+  Carver c{base};
+  const size_t D = v->D, Kp = v->Kp, Mx = (size_t)v->max_batch * v->T;
+  v->w_patch32 = c.take<float>(D * Kp); v->w_patchT32 = c.take<float>(D * Kp);
+  for (auto& l : v->layers) {
+    l.w_qkv32 = c.take<float>(3 * D * D); l.w_qkvT32 = c.take<float>(3 * D * D);
+    l.w_o32 = c.take<float>(D * D); l.w_oT32 = c.take<float>(D * D);
+    l.w_fc1_32 = c.take<float>(4 * D * D); l.w_fc1T32 = c.take<float>(4 * D * D);
+    l.w_fc2_32 = c.take<float>(4 * D * D); l.w_fc2T32 = c.take<float>(4 * D * D);
+    l.qkv32 = c.take<float>(Mx * 3 * D); l.dg32 = c.take<float>(Mx * 4 * D);
+  }
+  v->h32 = c.take<float>(Mx * D); v->g32 = c.take<float>(Mx * 4 * D);
+  v->att32 = c.take<float>(Mx * D); v->datt32 = c.take<float>(Mx * D); v->dqkv32 = c.take<float>(Mx * 3 * D);
+  v->delta32 = c.take<float>((size_t)v->max_batch * v->heads * v->T);
+  v->f32sp.ws_floats = (size_t)8 * v->max_batch * 4 * D;
+  v->f32sp.ws = c.take<float>(v->f32sp.ws_floats);
+  if (!base) v->f32sp.ws = nullptr;
+  *total = c.off;
 }
 
 void carve(aph_vit* v, char* base, size_t* total) {
@@ -147,6 +185,34 @@ int upload_f32(float* dst, const float* src, size_t rows, size_t cols, bool tran
   return hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
 
+// fp32 arena slots of a weight matrix (its [N, K] copy and the transpose) by checkpoint key; rows / cols of the [N, K] copy
+bool f32_slots(aph_vit* v, const std::string& n, float** w, float** wt, size_t* rows, size_t* cols) {
+  const size_t D = v->D;
+  if (n == "conv1.weight") { *w = v->w_patch32; *wt = v->w_patchT32; *rows = D; *cols = v->Kp; return true; }
+  const size_t p0 = strlen("transformer.resblocks.");
+  if (n.rfind("transformer.resblocks.", 0) != 0) return false;
+  const size_t dot = n.find('.', p0);
+  if (dot == std::string::npos) return false;
+  const int li = atoi(n.substr(p0, dot - p0).c_str());
+  if (li < 0 || li >= v->L) return false;
+  Layer& l = v->layers[li];
+  const std::string k = n.substr(dot + 1);
+  if (k == "attn.in_proj_weight") { *w = l.w_qkv32; *wt = l.w_qkvT32; *rows = 3 * D; *cols = D; return true; }
+  if (k == "attn.out_proj.weight") { *w = l.w_o32; *wt = l.w_oT32; *rows = D; *cols = D; return true; }
+  if (k == "mlp.c_fc.weight") { *w = l.w_fc1_32; *wt = l.w_fc1T32; *rows = 4 * D; *cols = D; return true; }
+  if (k == "mlp.c_proj.weight") { *w = l.w_fc2_32; *wt = l.w_fc2T32; *rows = D; *cols = 4 * D; return true; }
+  return false;
+}
+// host fp32 copy of a weight matrix -> the fp32 arena (when it exists)
+int sync_f32(aph_vit* v, const std::string& n) {
+  if (!v->arena_f32) return 0;
+  auto it = v->host32.find(n);
+  float *w = nullptr, *wt = nullptr;
+  size_t rows = 0, cols = 0;
+  if (it == v->host32.end() || !f32_slots(v, n, &w, &wt, &rows, &cols)) return 0;
+  return upload_f32(w, it->second.data(), rows, cols, false) | upload_f32(wt, it->second.data(), rows, cols, true);
+}
+
 // a launch of the GEMM family, with its HIP event pair when the profile is on (bench.py roofline); flops = its algorithmic FLOPs
 template <class F>
 void vtimed(aph_vit* v, double flops, hipStream_t st, F&& launch) {
@@ -167,6 +233,12 @@ void vtimed(aph_vit* v, double flops, hipStream_t st, F&& launch) {
 template <class Epi>
 void vgemm(aph_vit* v, const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st, int kdiv = 1) {
   vtimed(v, 2.0 * M * N * K / kdiv, st, [&] { launch_gemm(A, lda, Bt, ldb, M, N, K, epi, st, &v->sk); });
+}
+
+// the exact path's GEMMs (vit_gemm_f32.h), timed like vgemm
+template <class Epi>
+void vgemm32(aph_vit* v, const float* A, int lda, const float* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st, int a_rowP = 0) {
+  vtimed(v, 2.0 * M * N * K, st, [&] { launch_gemm_f32(A, lda, Bt, ldb, M, N, K, epi, st, &v->f32sp, a_rowP); });
 }
 
 #ifdef APH_EXPERIMENTS
@@ -376,6 +448,7 @@ int aph_vit_destroy(aph_vit* v) {
   for (hipEvent_t e : v->prof_ev) (void)hipEventDestroy(e);
   (void)hipFree(v->arena);
   if (v->arena_hilo) (void)hipFree(v->arena_hilo);
+  if (v->arena_f32) (void)hipFree(v->arena_f32);
   delete v;
   return APH_OK;
 }
@@ -407,7 +480,35 @@ int aph_vit_enable_hilo(aph_vit* v) {
   APH_CATCH
 }
 
-size_t aph_vit_workspace_bytes(const aph_vit* v) { return v ? v->arena_bytes + v->arena_hilo_bytes : 0; }
+// Allocates the exact path's arena (carve_f32) and fills its fp32 weights from the host fp32 copies aph_vit_set_weight keeps; a later
+// aph_vit_set_weight refreshes them.  Once, after the weights are loaded and outside any stream capture (allocates and copies synchronously);
+// idempotent.
+int aph_vit_enable_f32(aph_vit* v) {
+  APH_TRY
+  if (!v) return aph_fail(APH_ERR_ARG, "aph_vit_enable_f32: null handle");
+  if (v->arena_f32) return APH_OK;
+  if (v->n_set < 8 + 12 * v->L) return aph_fail(APH_ERR_ARG, "aph_vit_enable_f32: weights not fully loaded (%d tensors)", v->n_set);
+  size_t total = 0;
+  carve_f32(v, nullptr, &total);
+  char* base = nullptr;
+  const hipError_t me = hipMalloc((void**)&base, total);
+  if (me != hipSuccess) return aph_fail(APH_ERR_HIP, "aph_vit_enable_f32: cannot allocate %zu bytes (%s)", total, hipGetErrorString(me));
+  carve_f32(v, base, &total);
+  v->arena_f32 = base;
+  int rc = 0;
+  for (const auto& kv : v->host32) rc |= sync_f32(v, kv.first);
+  if (rc || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(base);
+    v->arena_f32 = nullptr;
+    carve_f32(v, nullptr, &total);           // back to null pointers
+    return aph_fail(APH_ERR_HIP, "aph_vit_enable_f32: weight upload failed");
+  }
+  v->arena_f32_bytes = total;
+  return APH_OK;
+  APH_CATCH
+}
+
+size_t aph_vit_workspace_bytes(const aph_vit* v) { return v ? v->arena_bytes + v->arena_hilo_bytes + v->arena_f32_bytes : 0; }
 
 // Upload one tensor by its OpenAI checkpoint key (without the `visual.` prefix), fp32 host data.
 // e.g. "conv1.weight", "transformer.resblocks.3.attn.in_proj_weight", "proj".
@@ -427,6 +528,8 @@ int aph_vit_set_weight(aph_vit* v, const char* name, const float* data, size_t c
       for (size_t c = 0; c < 3; ++c)
         for (size_t q = 0; q < pp; ++q) perm[d * Kp + q * 3 + c] = data[d * Kp + c * pp + q];
     rc = upload_f16(v->w_patch, perm.data(), D, Kp, false) | upload_f16(v->w_patchT, perm.data(), D, Kp, true) | (v->w_patch2 ? upload_f16_twice(v->w_patch2, perm.data(), D, Kp) : 0);
+    v->host32[n] = std::move(perm);
+    rc |= sync_f32(v, n);
   }
   else if (n == "class_embedding") { if ((rc = need(D))) return rc; rc = upload_f32(v->cls, data, 1, D, false); }
   else if (n == "positional_embedding") { if ((rc = need(T * D))) return rc; rc = upload_f32(v->pos, data, T, D, false); }
@@ -456,6 +559,10 @@ int aph_vit_set_weight(aph_vit* v, const char* name, const float* data, size_t c
     else if (k == "mlp.c_proj.weight") { if ((rc = need(4 * D * D))) return rc; rc = upload_f16(l.w_fc2, data, D, 4 * D, false) | upload_f16(l.w_fc2T, data, D, 4 * D, true); }
     else if (k == "mlp.c_proj.bias") { if ((rc = need(D))) return rc; rc = upload_f32(l.b_fc2, data, 1, D, false); }
     else return aph_fail(APH_ERR_ARG, "aph_vit_set_weight: unknown key %s", name);
+    if (k == "attn.in_proj_weight" || k == "attn.out_proj.weight" || k == "mlp.c_fc.weight" || k == "mlp.c_proj.weight") {
+      v->host32[n].assign(data, data + count);
+      rc |= sync_f32(v, n);
+    }
   } else return aph_fail(APH_ERR_ARG, "aph_vit_set_weight: unknown key %s", name);
   if (rc) return aph_fail(APH_ERR_HIP, "aph_vit_set_weight(%s): upload failed", name);
   v->n_set++;
@@ -536,6 +643,7 @@ static int vit_forward_impl(aph_vit* v, const void* d_patches, int S, float* d_e
   APH_ALLOW_SMEM(head_fwd_kernel, sizeof(float) * kHeadCuts * (D + 8 * 128));
   APH_LAUNCH(head_fwd_kernel, dim3((S + kHeadCuts - 1) / kHeadCuts, (v->E + 127) / 128), dim3(1024), sizeof(float) * kHeadCuts * (D + 8 * 128), st,
              (const float*)v->x_last, (const float*)v->ln_post_g, (const float*)v->ln_post_b, (const float*)v->proj, d_enc, S, T, D, v->E);
+  v->last_fwd = 1;
   return aph_check_launch("aph_vit_forward");
 }
 int aph_vit_forward(aph_vit* v, const void* d_patches, int S, float* d_enc, void* stream_) {
@@ -555,6 +663,8 @@ int aph_vit_forward_hilo(aph_vit* v, const void* d_patches_hilo, int S, float* d
 static int vit_backward_impl(aph_vit* v, const float* d_genc, int S, void* d_patch_grad, bool grad_f16, float out_scale, void* stream_) {
   if (!v || !d_genc || !d_patch_grad) return aph_fail(APH_ERR_ARG, "aph_vit_backward: null argument");
   if (S < 1 || S > v->max_batch) return aph_fail(APH_ERR_ARG, "aph_vit_backward: batch %d outside 1..%d", S, v->max_batch);
+  if (v->last_fwd == 2)
+    return aph_fail(APH_ERR_ARG, "aph_vit_backward: the last forward was aph_vit_forward_f32 (exact path): take its gradient with aph_vit_backward_f32");
   hipStream_t st = (hipStream_t)stream_;
   const int D = v->D, T = v->T, M = S * T, nv = D / 256;
   v->sk.small_batch = M <= 128;   // see gemm_rs_mode(): the split-K small-M kernel only when the whole batch is small
@@ -620,6 +730,80 @@ int aph_vit_backward(aph_vit* v, const float* d_genc, int S, float* d_patch_grad
 int aph_vit_backward_h(aph_vit* v, const float* d_genc, int S, void* d_patch_grad_f16, float out_scale, void* stream_) {
   APH_TRY
   return vit_backward_impl(v, d_genc, S, d_patch_grad_f16, true, out_scale, stream_);
+  APH_CATCH
+}
+
+// ---- exact path: fp32 operands everywhere, the f32-input MFMA GEMM (vit_gemm_f32.h), fp32 attention (vit_attn_f32.h), the fp32 LayerNorm
+// kernels of the f16 path with fp32 outputs / gradients.  Same block structure as vit_forward_impl (the last block on its class rows only).
+
+// d_patches f32 [S*P, 3*patch^2] (APH_OUT_PATCH_F32) -> d_enc f32 [S, output_dim]
+int aph_vit_forward_f32(aph_vit* v, const float* d_patches, int S, float* d_enc, void* stream_) {
+  APH_TRY
+  if (!v || !d_patches || !d_enc) return aph_fail(APH_ERR_ARG, "aph_vit_forward_f32: null argument");
+  if (S < 1 || S > v->max_batch) return aph_fail(APH_ERR_ARG, "aph_vit_forward_f32: batch %d outside 1..%d", S, v->max_batch);
+  if (v->n_set < 8 + 12 * v->L) return aph_fail(APH_ERR_ARG, "aph_vit_forward_f32: weights not fully loaded (%d tensors)", v->n_set);
+  if (!v->arena_f32)
+    return aph_fail(APH_ERR_ARG, "aph_vit_forward_f32: call aph_vit_enable_f32(vit) once after loading the weights (the exact path's fp32 weights "
+                    "and activations are not allocated by default)");
+  hipStream_t st = (hipStream_t)stream_;
+  const int D = v->D, T = v->T, M = S * T, nv = D / 256;
+  vgemm32(v, d_patches, v->Kp, v->w_patch32, v->Kp, S * v->P, D, v->Kp, EpiPatchEmbed{v->x0, v->pos, D, v->P, T}, st);
+  launch_ln_fwd<false, true>(nv, v->x0, v->ln_pre_g, v->ln_pre_b, v->layers[0].x_in, M, T, v->cls, v->pos, v->x0, st);
+  for (int li = 0; li < v->L; ++li) {
+    Layer& l = v->layers[li];
+    float* x_next = li + 1 < v->L ? v->layers[li + 1].x_in : v->x_last;
+    launch_ln_fwd<false, false>(nv, l.x_in, l.ln1_g, l.ln1_b, v->h32, M, T, nullptr, nullptr, nullptr, st);
+    vgemm32(v, v->h32, D, l.w_qkv32, D, M, 3 * D, D, EpiBiasF32{l.qkv32, 3 * D, l.b_qkv}, st);
+    launch_attn_fwd_f32(l.qkv32, v->att32, l.lse, S, T, v->heads, st);
+    const bool cls_only = li + 1 == v->L;
+    const int Mr = cls_only ? S : M, rs = cls_only ? T : 1;
+    vgemm32(v, v->att32, rs * D, l.w_o32, D, Mr, D, D, EpiResidual{l.x_mid, l.x_in, rs * D, l.b_o}, st);
+    launch_ln_fwd<false, false>(nv, l.x_mid, l.ln2_g, l.ln2_b, v->h32, Mr, T, nullptr, nullptr, nullptr, st, rs);
+    vgemm32(v, v->h32, D, l.w_fc1_32, D, Mr, 4 * D, D, EpiGeluF32{l.dg32, v->g32, 4 * D, l.b_fc1}, st);
+    vgemm32(v, v->g32, 4 * D, l.w_fc2_32, 4 * D, Mr, D, 4 * D, EpiResidual{x_next, l.x_mid, rs * D, l.b_fc2}, st);
+  }
+  APH_ALLOW_SMEM(head_fwd_kernel, sizeof(float) * kHeadCuts * (D + 8 * 128));
+  APH_LAUNCH(head_fwd_kernel, dim3((S + kHeadCuts - 1) / kHeadCuts, (v->E + 127) / 128), dim3(1024), sizeof(float) * kHeadCuts * (D + 8 * 128), st,
+             (const float*)v->x_last, (const float*)v->ln_post_g, (const float*)v->ln_post_b, (const float*)v->proj, d_enc, S, T, D, v->E);
+  v->last_fwd = 2;
+  return aph_check_launch("aph_vit_forward_f32");
+  APH_CATCH
+}
+
+// input-gradient of the last aph_vit_forward_f32: d_genc f32 [S, output_dim] -> d_patch_grad f32 [S*P, 3*patch^2] x out_scale.  The gradient
+// stream is fp32 end to end (no f16 copies); a power-of-two loss scale on d_genc and its inverse in out_scale are exact.
+int aph_vit_backward_f32(aph_vit* v, const float* d_genc, int S, float* d_patch_grad, float out_scale, void* stream_) {
+  APH_TRY
+  if (!v || !d_genc || !d_patch_grad) return aph_fail(APH_ERR_ARG, "aph_vit_backward_f32: null argument");
+  if (S < 1 || S > v->max_batch) return aph_fail(APH_ERR_ARG, "aph_vit_backward_f32: batch %d outside 1..%d", S, v->max_batch);
+  if (v->last_fwd != 2 || !v->arena_f32)
+    return aph_fail(APH_ERR_ARG, "aph_vit_backward_f32: the last forward was not aph_vit_forward_f32 (run the exact forward first; the f16 "
+                    "forward's gradient is aph_vit_backward)");
+  hipStream_t st = (hipStream_t)stream_;
+  const int D = v->D, T = v->T, M = S * T, nv = D / 256;
+  float* dh = v->h32;          // gradient w.r.t. a LayerNorm output [M, D]
+  float* du = v->g32;          // gradient w.r.t. the fc1 pre-activation [M, 4D]
+  // class rows of dx (the gradient w.r.t. the last block's output); the f16 copy the kernel also writes is not read here
+  APH_LAUNCH(head_bwd_kernel, dim3(S), dim3(D), sizeof(float) * v->E, st, d_genc, (const float*)v->x_last,
+             (const float*)v->ln_post_g, (const float*)v->projT, v->dx, v->dx16, T, D, v->E);
+  for (int li = v->L - 1; li >= 0; --li) {
+    Layer& l = v->layers[li];
+    const bool cls_only = li + 1 == v->L;
+    const int Mr = cls_only ? S : M, rs = cls_only ? T : 1;
+    if (cls_only) zero_fill_async(v->datt32, sizeof(float) * (size_t)M * D, st);      // no gradient into the other rows' attention output
+    vgemm32(v, v->dx, rs * D, l.w_fc2T32, D, Mr, 4 * D, D, EpiGeluBwdF32{du, l.dg32, 4 * D}, st);
+    vgemm32(v, du, 4 * D, l.w_fc1T32, 4 * D, Mr, D, 4 * D, EpiF32{dh, D, 1.0f}, st);
+    launch_ln_bwd<false, false>(nv, dh, l.x_mid, l.ln2_g, v->dx, v->dx, nullptr, Mr, T, st, rs);
+    vgemm32(v, v->dx, rs * D, l.w_oT32, D, Mr, D, D, EpiF32{v->datt32, rs * D, 1.0f}, st);
+    launch_attn_bwd_f32(l.qkv32, v->datt32, l.lse, v->delta32, v->dqkv32, S, T, v->heads, st);
+    vgemm32(v, v->dqkv32, 3 * D, l.w_qkvT32, 3 * D, M, D, 3 * D, EpiF32{dh, D, 1.0f}, st);
+    // the last block's residual reaches its class rows only (res_T = T): the other rows of dx are not read before this writes them
+    launch_ln_bwd<false, false>(nv, dh, l.x_in, l.ln1_g, v->dx, v->dx, nullptr, M, T, st, 1, cls_only ? T : 0);
+  }
+  // ln_pre backward into dh (token rows), then the patch-embedding dgrad over its patch rows (row s*P + p <- token row s*T + 1 + p)
+  launch_ln_bwd<false, false>(nv, v->dx, v->x0, v->ln_pre_g, nullptr, dh, nullptr, M, T, st);
+  vgemm32(v, dh, D, v->w_patchT32, D, S * v->P, v->Kp, D, EpiF32{d_patch_grad, v->Kp, out_scale}, st, v->P);
+  return aph_check_launch("aph_vit_backward_f32");
   APH_CATCH
 }
 
@@ -838,6 +1022,27 @@ int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_da
   if (mode == 0) launch_attn_fwd(a, (hipStream_t)stream_);
   else launch_attn_bwd(a, (hipStream_t)stream_);
   return aph_check_launch("aph_attn_test");
+  APH_CATCH
+}
+
+// the exact path's GEMM alone (unit tests, micro-benchmarks): C = epilogue(A * Bt^T), f32 in and out.  epi_kind 0 = plain (C pitch ldc), 1 = + bias,
+// 2 = QuickGELU (C = g, d_aux = dg/du), 3 = GELU backward (C = acc * d_aux), 4 = residual (C = d_aux + acc + bias, pitch ldc).  d_ws / ws_floats:
+// split-K workspace (NULL: never split).  a_rowP > 0: A row m read from row m + m / a_rowP + 1.
+int aph_gemm_f32_test(const float* d_A, int lda, int a_rowP, const float* d_Bt, int ldb, int M, int N, int K, float* d_C, int ldc, const float* d_bias,
+                      float* d_aux, int epi_kind, float* d_ws, size_t ws_floats, void* stream_) {
+  APH_TRY
+  if (!d_A || !d_Bt || !d_C || !gemm_f32_shape_ok(M, N, K, lda, ldb) || ldc < N || ldc % 4 || a_rowP < 0 || epi_kind < 0 || epi_kind > 4 ||
+      ((epi_kind == 1 || epi_kind == 2 || epi_kind == 4) && !d_bias) || (epi_kind >= 2 && !d_aux))
+    return aph_fail(APH_ERR_ARG, "aph_gemm_f32_test: bad argument (need N %% 128 == 0, K %% 32 == 0, pitches %% 4 == 0; M=%d N=%d K=%d)", M, N, K);
+  F32Space sp;
+  sp.ws = d_ws; sp.ws_floats = d_ws ? ws_floats : 0;
+  hipStream_t st = (hipStream_t)stream_;
+  if (epi_kind == 0) launch_gemm_f32(d_A, lda, d_Bt, ldb, M, N, K, EpiF32{d_C, ldc, 1.0f}, st, &sp, a_rowP);
+  else if (epi_kind == 1) launch_gemm_f32(d_A, lda, d_Bt, ldb, M, N, K, EpiBiasF32{d_C, ldc, d_bias}, st, &sp, a_rowP);
+  else if (epi_kind == 2) launch_gemm_f32(d_A, lda, d_Bt, ldb, M, N, K, EpiGeluF32{d_aux, d_C, ldc, d_bias}, st, &sp, a_rowP);
+  else if (epi_kind == 3) launch_gemm_f32(d_A, lda, d_Bt, ldb, M, N, K, EpiGeluBwdF32{d_C, d_aux, ldc}, st, &sp, a_rowP);
+  else launch_gemm_f32(d_A, lda, d_Bt, ldb, M, N, K, EpiResidual{d_C, d_aux, ldc, d_bias}, st, &sp, a_rowP);
+  return aph_check_launch("aph_gemm_f32_test");
   APH_CATCH
 }
 

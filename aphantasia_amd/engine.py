@@ -38,7 +38,7 @@ class Engine:
                  lr=0.05, optimizer='adam_custom', align='uniform', macro=0.4, transform=None,
                  size=None, rank=0, world=1, process_group=None, comm=None, param_kind='fft', decorrelate=True, lib=None, state=None, dwt=None, rng='bulk', use_graph=True,
                  rgb_priors=None, fixcontrast=False, sharp=0.0, expand=0.0, enforce=0.0, grad_f16=False, loss_scale=None, reduce_always=False, aest=None,
-                 precise=False, graph_allreduce=None):
+                 precise=False, graph_allreduce=None, exact=False):
         """params: the leaf tensor ([1,3,h,w//2+1,2] spectrum for 'fft', [1,3,h,w] for 'pixel', the flat
         coefficient buffer for 'dwt' with dwt = its aphantasia_amd.dwt.DWTSynth);
         model: aphantasia_amd.clip.CLIPModel; targets: list of (embedding [1,D] tensor, coef) with
@@ -48,6 +48,9 @@ class Engine:
         global generators (a seeded run then reproduces the reference's crop tables; costs milliseconds of Python).
         precise: the opt-in split-precision ViT forward (aph_vit_forward_hilo: the cuts and every block's first LayerNorm output as hi + lo
         f16 pairs -- the two roundings that dominate the gradient error on weights with realistic dynamic range; ~8 % slower at C2).
+        exact: the fp32 ViT path (aph_vit_forward_f32 / aph_vit_backward_f32: f32-input MFMA GEMMs, fp32 attention, activations and gradient
+        stream) on fp32 cuts (APH_OUT_PATCH_F32); the model's weights are used in full fp32.  The power-of-two loss scale is kept: scaling by
+        it and by its inverse is exact in fp32.  Exclusive with `precise` and `grad_f16`.
         graph_allreduce: with world > 1 and a direct RCCL `comm`, capture the whole step INCLUDING its all-reduce into one hipGraph.  OPT-IN
         (default: the environment's APH_MULTIRANK_GRAPH=1, else off -> multi-rank steps launch eagerly): until that path has executed on a
         real multi-GPU node a hang inside the capture or its collectives would take a run down without an exception to catch (ADVICE r5);
@@ -135,7 +138,12 @@ class Engine:
         self.m, self.v, self.vmax = state['m'], state['v'], state['vmax']
         self.set_targets(targets)
         # static buffers
+        if exact and (precise or grad_f16):
+            raise ValueError('Engine: exact=True is exclusive with precise / grad_f16 (the exact path is fp32 end to end)')
+        self.exact = bool(exact)
         self.visual.ensure_batch(max(self.S_loc, 1))
+        if self.exact:
+            self.visual.handle.enable_f32()           # allocates the fp32 arena: here, not inside a captured step
         if precise:
             self.visual.handle.enable_hilo()          # allocates the K-repeated weight copies: here, not inside a captured step
         g = self.size // self.patch
@@ -145,8 +153,8 @@ class Engine:
         self.raw = torch.empty(3, h, w, **f32)
         self.rgb = torch.empty(3, h, w, **f32)
         self.precise = bool(precise)
-        self._patch_mode = _ffi.APH_OUT_PATCH_F16_HILO if self.precise else _ffi.APH_OUT_PATCH_F16
-        self.patches = torch.empty(Sl * self.P, (2 if self.precise else 1) * self.Kp, dtype=torch.float16, device=self.dev)
+        self._patch_mode = _ffi.APH_OUT_PATCH_F32 if self.exact else (_ffi.APH_OUT_PATCH_F16_HILO if self.precise else _ffi.APH_OUT_PATCH_F16)
+        self.patches = torch.empty(Sl * self.P, (2 if self.precise else 1) * self.Kp, dtype=torch.float32 if self.exact else torch.float16, device=self.dev)
         # ViT input-gradient handed to the sampler adjoint: f32 (default, exact path) or f16 carrying the loss scale
         # (measured: -1.6 % step time at C2, 5e-4 relative rounding per gradient element)
         self.grad_f16 = bool(grad_f16)
@@ -291,7 +299,7 @@ class Engine:
         if Sl > 0:
             L.call('aph_sample_fwd', ctypes_byref(self.geom), ops.ptr(self.rgb), ops.ptr(self.table), ops.ptr(self.aug), ops.ptr(self.tmp),
                    ops.ptr(self.patches), self._patch_mode, st)
-            self.visual._forward_patches(self.patches, Sl, self.enc, hilo=self.precise)
+            self.visual._forward_patches(self.patches, Sl, self.enc, hilo=self.precise, f32=self.exact)
             L.call('aph_sim_loss', ops.ptr(self.enc), Sl, self.enc.shape[1], ops.ptr(self.targets), ops.ptr(self.dcoef), self.hcoef,
                    len(self.coef), self.n_broadcast, self.S, self.lo, _ffi.SIM_TYPES[ops._sim_key(self.sim)], float(self.S), self.loss_scale, ops.ptr(self.ws),
                    ops.ptr(self.loss), ops.ptr(self.genc), st)
@@ -300,7 +308,7 @@ class Engine:
                        float(self.S), self.loss_scale, ops.ptr(self.loss), ops.ptr(self.genc), st)
             if self.enforce != 0:
                 self._enqueue_enforce(L, st, Sl)
-            self.visual.handle.backward(self.genc, Sl, self.gpatch, vit_scale)
+            self.visual.handle.backward(self.genc, Sl, self.gpatch, vit_scale, f32=self.exact)
             L.call('aph_sample_bwd', ctypes_byref(self.geom), ops.ptr(self.gpatch), smp_scale, ops.ptr(self.table), ops.ptr(self.aug),
                    ops.ptr(self.tmp), ops.ptr(self.grgb), gmode, st)
             if self.enforce != 0:
@@ -330,6 +338,8 @@ class Engine:
         loss scale (range) and the sampler adjoint removes it"""
         if self.grad_f16:
             return 1.0, 1.0 / self.loss_scale, _ffi.APH_GRAD_PATCH_F16
+        if self.exact:
+            return 1.0 / self.loss_scale, 1.0, _ffi.APH_OUT_PATCH_F32
         return 1.0 / self.loss_scale, 1.0, _ffi.APH_OUT_PATCH_F16
 
     def _enqueue_enforce(self, L, st, Sl):
@@ -346,17 +356,17 @@ class Engine:
                    self.loss_scale, ops.ptr(self.ws2), ops.ptr(loss), ops.ptr(genc), st)
         L.call('aph_sample_fwd', ctypes_byref(self.geom), ops.ptr(self.rgb), ops.ptr(self.table2), ops.ptr(self.aug2), ops.ptr(self.tmp),
                ops.ptr(self.patches), self._patch_mode, st)
-        self.visual._forward_patches(self.patches, Sl, self.enc2, hilo=self.precise)
+        self.visual._forward_patches(self.patches, Sl, self.enc2, hilo=self.precise, f32=self.exact)
         pair_term(self.enc2, self.enc, self.loss2, self.genc2)
         vit_scale, smp_scale, gmode = self._grad_modes()
-        self.visual.handle.backward(self.genc2, Sl, self.gpatch, vit_scale)
+        self.visual.handle.backward(self.genc2, Sl, self.gpatch, vit_scale, f32=self.exact)
         L.call('aph_sample_bwd', ctypes_byref(self.geom), ops.ptr(self.gpatch), smp_scale, ops.ptr(self.table2), ops.ptr(self.aug2),
                ops.ptr(self.tmp), ops.ptr(self.grgb2), gmode, st)
         pair_term(self.enc, self.enc2, self.loss2, self.genc2)       # same value again; genc2 now = d/d enc (first set)
         L.call('aph_axpy_f32', ops.ptr(self.genc), ops.ptr(self.genc2), 1.0, self.genc.numel(), st)
         L.call('aph_sample_fwd', ctypes_byref(self.geom), ops.ptr(self.rgb), ops.ptr(self.table), ops.ptr(self.aug), ops.ptr(self.tmp),
                ops.ptr(self.patches), self._patch_mode, st)
-        self.visual._forward_patches(self.patches, Sl, self.enc, hilo=self.precise)
+        self.visual._forward_patches(self.patches, Sl, self.enc, hilo=self.precise, f32=self.exact)
 
     def _stepin_views(self, flat):
         return {name: flat[o:o + n].view(dt).view(shape) for name, o, n, shape, dt in self._stepin_layout}

@@ -132,6 +132,9 @@ def make_geom(H, W, S, size, patch=32, align='uniform'):
 
 
 def sample_out_shape(geom, out_mode):
+    if out_mode == _ffi.APH_OUT_PATCH_F32:
+        g = geom.size // geom.patch
+        return (geom.S * g * g, 3 * geom.patch * geom.patch), torch.float32
     if out_mode in (_ffi.APH_OUT_PATCH_F16, _ffi.APH_OUT_PATCH_F16_HILO):
         g = geom.size // geom.patch
         kx = 2 if out_mode == _ffi.APH_OUT_PATCH_F16_HILO else 1           # rows [hi | lo] of the split-precision forward
@@ -171,12 +174,17 @@ def sample_bwd(geom, gout, table, aug=None, tmp=None, out=None, out_mode=_ffi.AP
     return out
 
 
-def patchify(x, patch, lib=None, hilo=False):
-    """NCHW f32 -> the patch-embed GEMM operand; hilo: rows [hi | lo] for VitHandle.forward(..., hilo=True)"""
+def patchify(x, patch, lib=None, hilo=False, f32=False):
+    """NCHW f32 -> the patch-embed GEMM operand; hilo: rows [hi | lo] for VitHandle.forward(..., hilo=True);
+    f32: fp32 rows (values unchanged) for VitHandle.forward(..., f32=True)"""
     L = _L(lib, x)
     _chk(x, torch.float32, 'x')
     S, _, R, _ = x.shape
     g = R // patch
+    if f32:
+        out = torch.empty(S * g * g, 3 * patch * patch, dtype=torch.float32, device=x.device)
+        L.call('aph_patchify_f32', ptr(x), S, R, patch, ptr(out), _stream(x))
+        return out
     out = torch.empty(S * g * g, (2 if hilo else 1) * 3 * patch * patch, dtype=torch.float16, device=x.device)
     L.call('aph_patchify_f16_hilo' if hilo else 'aph_patchify_f16', ptr(x), S, R, patch, ptr(out), _stream(x))
     return out
@@ -208,6 +216,15 @@ class VitHandle:
         g = cfg['input_resolution'] // cfg['patch_size']
         self.P, self.T, self.Kp = g * g, g * g + 1, 3 * cfg['patch_size'] ** 2
         self._hilo = False
+        self._f32 = False
+
+    def enable_f32(self):
+        """the exact path's arena (aph_vit_enable_f32): fp32 weights and transposes, fp32 activation stash"""
+        if not self._f32:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('VitHandle.enable_f32() allocates: call it before the step is captured into a graph')
+            self.lib.call('aph_vit_enable_f32', self.handle)
+            self._f32 = True
 
     def enable_hilo(self):
         """the K-repeated weight copies of the split-precision forward (aph_vit_enable_hilo: 85 MB at ViT-B/32, not carried by default)"""
@@ -220,10 +237,19 @@ class VitHandle:
     def workspace_bytes(self):
         return int(self.lib.cdll.aph_vit_workspace_bytes(self.handle))
 
-    def forward(self, patches, S, out=None, hilo=False):
-        """hilo: the opt-in split-precision forward (aph_vit_forward_hilo); `patches` then holds [hi | lo] rows (APH_OUT_PATCH_F16_HILO)"""
+    def forward(self, patches, S, out=None, hilo=False, f32=False):
+        """hilo: the opt-in split-precision forward (aph_vit_forward_hilo); `patches` then holds [hi | lo] rows (APH_OUT_PATCH_F16_HILO).
+        f32: the exact forward (aph_vit_forward_f32) on fp32 patch rows (APH_OUT_PATCH_F32); needs enable_f32() first"""
         if out is None:
             out = torch.empty(S, self.cfg['output_dim'], dtype=torch.float32, device=patches.device)
+        if f32:
+            if hilo:
+                raise ValueError('VitHandle.forward: hilo and f32 are exclusive')
+            _chk(patches, torch.float32, 'patches')
+            if patches.shape[-1] != self.Kp:
+                raise ValueError('VitHandle.forward(f32=True): patch rows of %d floats, expected %d' % (patches.shape[-1], self.Kp))
+            self.lib.call('aph_vit_forward_f32', self.handle, ptr(patches), int(S), ptr(out), _stream(patches))
+            return out
         want = (2 if hilo else 1) * self.Kp
         if patches.shape[-1] != want:
             raise ValueError('VitHandle.forward(hilo=%s): patch rows of %d halfs, expected %d' % (hilo, patches.shape[-1], want))
@@ -232,9 +258,14 @@ class VitHandle:
         self.lib.call('aph_vit_forward_hilo' if hilo else 'aph_vit_forward', self.handle, ptr(patches), int(S), ptr(out), _stream(patches))
         return out
 
-    def backward(self, genc, S, out=None, out_scale=1.0):
+    def backward(self, genc, S, out=None, out_scale=1.0, f32=False):
+        """f32: the gradient of the exact forward (aph_vit_backward_f32); `out` is then f32"""
         if out is None:
             out = torch.empty(S * self.P, self.Kp, dtype=torch.float32, device=genc.device)
+        if f32:
+            _chk(out, torch.float32, 'out')
+            self.lib.call('aph_vit_backward_f32', self.handle, ptr(genc), int(S), ptr(out), float(out_scale), _stream(genc))
+            return out
         fn = 'aph_vit_backward_h' if out.dtype == torch.float16 else 'aph_vit_backward'        # f16 `out`: patch gradient kept in half
         self.lib.call(fn, self.handle, ptr(genc), int(S), ptr(out), float(out_scale), _stream(genc))
         return out

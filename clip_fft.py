@@ -78,6 +78,8 @@ def get_args(argv=None):
     parser.add_argument(       '--no_save', action='store_true', help='do not write the per-step JPEG frames')
     parser.add_argument(       '--precise', action='store_true', help='opt-in split-precision ViT forward (patch-embedding and QKV GEMMs on hi + lo f16 activation pairs): ~5 %% slower, lower single-step gradient error; '
                                'on the stress-weight loss-curve ensemble not significantly closer to the fp32 CPU reference than the default')
+    parser.add_argument(       '--exact', action='store_true', help='opt-in fp32 ViT (f32-input MFMA GEMMs, fp32 attention / activations / gradient stream): '
+                               'the reference\'s fp32 CPU numerics up to summation order; measured 26.3 steps/s at C2 (1280x720, 190 cuts, -tf fast) against ~160-174 for the default, i.e. ~6x the step time.  Exclusive with --precise')
     parser.add_argument(       '--fast-f16', action='store_true', help='(the default since round 6; accepted for old command lines) f16 operands on every ViT GEMM, as the reference runs CLIP on a GPU')
     parser.add_argument(       '--aest-weights', dest='aest_weights', default=None, help="state dict of the LAION aesthetic head (sa_0_4_vit_b_32_linear.pth: "
                                "{'weight': [1,512], 'bias': [1]}); upstream downloads it (utils.py:402-413), there is no network here")
@@ -91,6 +93,8 @@ def get_args(argv=None):
                                '(opt-in: multi-rank steps launch eagerly by default; same as APH_MULTIRANK_GRAPH=1)')
     parser.add_argument(       '--no-graph', action='store_true', help='eager launches instead of hipGraph replay (debugging)')
     a = parser.parse_args(argv)
+    if a.exact and a.precise:
+        parser.error('--exact and --precise are mutually exclusive (the exact path is fp32 end to end)')
 
     if a.size is not None: a.size = [int(s) for s in a.size.split('-')][::-1]        # clip_fft.py:80
     if len(a.size) == 1: a.size = a.size * 2
@@ -346,13 +350,13 @@ def main(argv=None):
         leaf = params[0]
     eng = Engine(leaf, h, w, model_clip, a.samples, targets, sim=a.sim, colors=a.colors, decay=a.decay, lr=lr0,
                  optimizer=a.optimizer, align=a.align, macro=a.macro, transform=trform_f, sharp=a.sharp, expand=a.expand, enforce=a.enforce, rng=a.rng,
-                 rank=rank, world=world, comm=comm, aest=aest1, precise=a.precise, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, **pk)
+                 rank=rank, world=world, comm=comm, aest=aest1, precise=a.precise, exact=a.exact, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, **pk)
     h, w = eng.h, eng.w
     eng2 = None
     if a.dualmod is not None:
         eng2 = Engine(leaf, h, w, model_clip2, a.samples, targets2, sim=a.sim, colors=a.colors, decay=a.decay, lr=lr0,
                       optimizer=a.optimizer, align=a.align, macro=a.macro, transform=trform_f, state=eng.state(), sharp=a.sharp, expand=a.expand, enforce=a.enforce, rng=a.rng,
-                      rank=rank, world=world, comm=comm, aest=aest2, precise=a.precise, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, **pk)
+                      rank=rank, world=world, comm=comm, aest=aest2, precise=a.precise, exact=a.exact, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, **pk)
 
     writer = None if a.no_save else FrameWriter(h, w)
     # empirical tone mapping of the saved frames (clip_fft.py:300-303): **1.3 with --sync, **(1 + sharp/2) with --sharp

@@ -77,6 +77,8 @@ def get_args(argv=None):
     p.add_argument('--ranks', default=1, type=int, help='GPUs of this node to shard the cuts over (launch with torchrun, or let this flag spawn the ranks)')
     p.add_argument('--graph-allreduce', action='store_true', help='with --ranks N: the step incl. its RCCL all-reduce as one hipGraph (opt-in; APH_MULTIRANK_GRAPH=1)')
     p.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay (debugging)')
+    p.add_argument('--exact', action='store_true', help='opt-in fp32 ViT (f32-input MFMA GEMMs, fp32 attention / activations / gradient stream): '
+                   'the reference\'s fp32 CPU numerics up to summation order; measured 26.3 steps/s at C2 (1280x720, 190 cuts, -tf fast) against ~160-174 for the default, i.e. ~6x the step time')
     a = p.parse_args(argv)
     a.size = [int(s) for s in a.size.split('-')][::-1]                    # illustrip.py:90-91
     if len(a.size) == 1: a.size = a.size * 2
@@ -174,7 +176,7 @@ def main(argv=None):
         leaf = (0.01 * torch.randn(1, 3, h, w // 2 + 1, 2)).cuda().contiguous()
         pk = dict(param_kind='fft', decay=1.0)                                                  # fft_image default decay_power (illustrip.py:409)
     kw = dict(sim=a.sim, colors=a.colors, lr=a.lrate, optimizer=a.optimizer, align=a.align, macro=a.macro, transform=trf, sharp=a.sharp,
-              expand=a.expand, enforce=a.enforce, rng=a.rng, rank=rank, world=world, comm=comm, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, **pk)
+              expand=a.expand, enforce=a.enforce, rng=a.rng, rank=rank, world=world, comm=comm, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, exact=a.exact, **pk)
     eng = Engine(leaf, h, w, model, S, targets_for(model), **kw)
     eng2 = Engine(leaf, h, w, model2, S, targets_for(model2), state=eng.state(), **kw) if model2 is not None else None
     depth_fn = None

@@ -120,6 +120,8 @@ typedef struct aph_sample_geom {
                               * k = (iy*patch + ix)*3 + c: pixel-major inside the patch, channel fastest (aph_vit_set_weight permutes conv1.weight to match) */
 #define APH_OUT_PATCH_F16_HILO 4 /* aph_sample_fwd only: APH_OUT_PATCH_F16 rows written as [hi (3*patch^2) | lo (3*patch^2)], hi = f16(x), lo = f16(x - hi):
                               * the operand of the split-precision forward aph_vit_forward_hilo */
+#define APH_OUT_PATCH_F32 5  /* the APH_OUT_PATCH_F16 row layout in f32 (the exact path, aph_vit_forward_f32); aph_sample_bwd: the gradient in the
+                              * same f32 patch-major layout (aph_vit_backward_f32) */
 #define APH_GRAD_PATCH_F16 3 /* aph_sample_bwd only: gradient in the patch-major layout stored as f16 (aph_vit_backward_h) */
 
 #define APH_AUG_STRIDE 16
@@ -165,6 +167,8 @@ int aph_grid_warp(const float* d_img, const float* d_depth, int C, int H, int W,
 int aph_patchify_f16(const float* d_nchw, int S, int R, int patch, void* d_patches_f16, void* stream);
 /* the same into the [hi | lo] rows of APH_OUT_PATCH_F16_HILO: d_patches_hilo f16 [S*(R/patch)^2, 2 * 3*patch^2] */
 int aph_patchify_f16_hilo(const float* d_nchw, int S, int R, int patch, void* d_patches_hilo, void* stream);
+/* the same in f32 (APH_OUT_PATCH_F32 layout, values unchanged): d_patches f32 [S*(R/patch)^2, 3*patch^2] */
+int aph_patchify_f32(const float* d_nchw, int S, int R, int patch, float* d_patches, void* stream);
 int aph_unpatchify_f32(const float* d_patch_grad, int S, int R, int patch, float gscale, float* d_nchw_grad, void* stream);
 
 /* ---- CLIP ViT visual tower: model.encode_image (clip_fft.py:254) + its input-gradient ----- */
@@ -192,6 +196,16 @@ int aph_vit_forward_hilo(aph_vit* vit, const void* d_patches_hilo, int S, float*
 /* [r6] Allocates and fills the K-repeated copies of the patch-embedding / QKV weights aph_vit_forward_hilo needs (85 MB at ViT-B/32; a handle
  * does not carry them by default).  Once per handle, after aph_vit_set_weight of every tensor, outside any stream capture; idempotent. */
 int aph_vit_enable_hilo(aph_vit* vit);
+/* EXACT path (opt-in: clip_fft.py --exact).  Allocates a separate arena with fp32 copies of the weight matrices (and their transposes), the
+ * fp32 activation stash and fp32 gradient buffers, filled from host fp32 copies aph_vit_set_weight keeps -- exact for any weights; a later
+ * aph_vit_set_weight refreshes them.  Once per handle, after aph_vit_set_weight of every tensor, outside any stream capture; idempotent. */
+int aph_vit_enable_f32(aph_vit* vit);
+/* fp32 forward: every GEMM on the f32-input MFMA (a k-ordered fmaf chain), fp32 attention / LayerNorm / GELU.  d_patches f32 [S*P, 3*patch^2]
+ * (APH_OUT_PATCH_F32) -> d_enc f32 [S, output_dim].  Refused (APH_ERR_ARG) before aph_vit_enable_f32. */
+int aph_vit_forward_f32(aph_vit* vit, const float* d_patches, int S, float* d_enc, void* stream);
+/* input-gradient of the last aph_vit_forward_f32 (refused after any other forward; aph_vit_backward is refused after this forward):
+ * d_genc f32 [S, output_dim] -> d_patch_grad f32 [S*P, 3*patch^2] x out_scale; fp32 gradient stream end to end */
+int aph_vit_backward_f32(aph_vit* vit, const float* d_genc, int S, float* d_patch_grad, float out_scale, void* stream);
 /* d_genc f32 [S, output_dim] (times the caller's loss scale) -> d_patch_grad f32 [S*P, 3*patch^2] times out_scale */
 int aph_vit_backward(aph_vit* vit, const float* d_genc, int S, float* d_patch_grad, float out_scale, void* stream);
 /* same with the patch gradient stored as f16 (keep the loss scale in it: out_scale = 1, and undo it in aph_sample_bwd's

@@ -21,6 +21,11 @@ int aph_vit_profile_read(aph_vit* vit, double* ms_total, long long* launches, do
 int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* d_delta, void* d_dqkv, int S, int T, int heads,
                   int mode, void* stream);
 /* C[M,N] f32 = A[M,K] f16 * Bt[N,K]^T f16 (N % 128 == 0, K % 64 == 0): the ViT GEMM core with the automatic tile choice */
+/* the exact path's f32-input MFMA GEMM alone: C = epilogue(A * Bt^T), f32 in / out.  epi_kind 0 = plain (pitch ldc), 1 = + bias, 2 = QuickGELU
+ * (C = g, d_aux = dg/du), 3 = GELU backward (C = acc * d_aux), 4 = residual (C = d_aux + acc + bias).  d_ws (ws_floats): split-K workspace or
+ * NULL (never split).  a_rowP > 0: A row m is read from row m + m / a_rowP + 1 (the patch rows of a token-major buffer). */
+int aph_gemm_f32_test(const float* d_A, int lda, int a_rowP, const float* d_Bt, int ldb, int M, int N, int K, float* d_C, int ldc,
+                      const float* d_bias, float* d_aux, int epi_kind, float* d_ws, size_t ws_floats, void* stream);
 int aph_gemm_f16(const void* d_A, const void* d_Bt, int M, int N, int K, float* d_C, void* stream);
 /* same with explicit row pitches (elements, multiples of 8) and an explicit tile configuration:
  *    0  automatic (the shape heuristic of launch_gemm)
