@@ -415,6 +415,50 @@ inline AttnArgs attn_args(aph_vit* v, const Layer& l, int S) {
 
 }  // namespace
 
+// the split-K workspace of the test entries' tile_cfg 8 / 9 / 22 / 24 (one per process, allocated on first use)
+static int gemm_test_splitk_space(SplitKSpace** out) {
+  static SplitKSpace sp;
+  if (!sp.ws) {
+    if (hipMalloc((void**)&sp.ws, ((size_t)4 << 24) * sizeof(float)) != hipSuccess) return aph_fail(APH_ERR_HIP, "GEMM test entry: split-K workspace");
+    sp.ws_floats = (size_t)4 << 24;
+  }
+  *out = &sp;
+  return 0;
+}
+
+// tile_cfg -> kernel family for the product's families (0, 1, 2, 5, 8, 9, 10, 14, 15), shared by aph_gemm_f16_ld and aph_gemm_f16_epi_test;
+// the shape limits of each family are the callers' to check.  0 = launch_gemm with `sp` (its split-K workspace and small_batch flag, or null).
+template <class Epi>
+static int gemm_f16_launch_cfg(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, Epi epi, int tile_cfg, const SplitKSpace* sp,
+                               hipStream_t st) {
+  switch (tile_cfg) {
+    case 0: launch_gemm(A, lda, B, ldb, M, N, K, epi, st, sp); break;
+    case 1: launch_gemm_cfg<GemmSmall>(A, lda, B, ldb, M, N, K, epi, st); break;
+    case 2: launch_gemm_cfg<GemmBig>(A, lda, B, ldb, M, N, K, epi, st); break;
+    case 5: launch_gemm_ws_cfg<GemmWS>(A, lda, B, ldb, M, N, K, epi, st, nullptr); break;
+    case 8:
+    case 9: {                // split-K (2 / 4 ways) of the 64x64 configuration, private workspace
+      SplitKSpace* ws = nullptr;
+      if (const int rc = gemm_test_splitk_space(&ws)) return rc;
+      launch_gemm_splitk<GemmSmall>(A, lda, B, ldb, M, N, K, epi, tile_cfg == 8 ? 2 : 4, *ws, st);
+      break;
+    }
+    case 10: launch_gemm_cfg<GemmMidDeep8>(A, lda, B, ldb, M, N, K, epi, st); break;
+    case 14: launch_gemm_sk<4>(A, lda, B, ldb, M, N, K, epi, st); break;
+    case 15: launch_gemm_sk<3>(A, lda, B, ldb, M, N, K, epi, st); break;
+    default: return aph_fail(APH_ERR_ARG, "GEMM test entry: tile_cfg %d is not a product kernel family", tile_cfg);
+  }
+  return 0;
+}
+// the shape limits of tile_cfg 5, 8 / 9 / 22 / 24 and 14 / 15 (false: refuse)
+static bool gemm_test_cfg_fits(int tile_cfg, int M, int lda, int N, int ldb, int K) {
+  if (tile_cfg == 5) return gemm8_addressable(M, lda, N, ldb) && N <= GemmWS::BIAS_MAX;
+  if (tile_cfg == 14 || tile_cfg == 15) return gemm8_addressable(M, lda, N, ldb) && gemm_sk_fits(N, K);
+  if (tile_cfg == 8 || tile_cfg == 9 || tile_cfg == 22 || tile_cfg == 24)
+    return K / GEMM_BK >= ((tile_cfg == 8 || tile_cfg == 22) ? 2 : 4) && (size_t)M * N <= ((size_t)1 << 24);
+  return true;
+}
+
 extern "C" {
 
 // cfg mirrors clip.model.VisionTransformer(input_resolution, patch_size, width, layers, heads, output_dim)
@@ -1072,7 +1116,8 @@ int aph_gemm_f16_ld(const void* d_A, int lda, const void* d_Bt, int ldb, int M, 
   tile_cfg &= 0xff;
   if (!d_A || !d_Bt || !d_C || M < 1 || N % 128 || K % GEMM_BK || N < 1 || K < 1 || lda < K || ldb < K || (lda & 7) || (ldb & 7) ||
       !(tile_cfg == 0 || tile_cfg == 1 || tile_cfg == 2 || tile_cfg == 4 || tile_cfg == 5 || (tile_cfg >= 8 && tile_cfg <= 12) || (tile_cfg >= 14 && tile_cfg <= 17) || tile_cfg == 22 || tile_cfg == 24) ||
-      (tile_cfg >= 14 && tile_cfg <= 17 && !gemm8_addressable(M, lda, N, ldb)) || (tile_cfg >= 14 && tile_cfg <= 15 && !gemm_sk_fits(N, K)) || (tile_cfg >= 16 && tile_cfg <= 17 && !gemm_ar_addressable(N, K)) || (tile_cfg == 4 && (N % 256 || !gemm8_addressable(M, lda, N, ldb))) || (tile_cfg == 5 && (!gemm8_addressable(M, lda, N, ldb) || N > GemmWS::BIAS_MAX)))
+      (tile_cfg >= 16 && tile_cfg <= 17 && (!gemm8_addressable(M, lda, N, ldb) || !gemm_ar_addressable(N, K))) || (tile_cfg == 4 && (N % 256 || !gemm8_addressable(M, lda, N, ldb))) ||
+      !gemm_test_cfg_fits(tile_cfg, M, lda, N, ldb, K))
     return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: bad shape");
   const half_t* A = (const half_t*)d_A;
   const half_t* B = (const half_t*)d_Bt;
@@ -1088,38 +1133,90 @@ int aph_gemm_f16_ld(const void* d_A, int lda, const void* d_Bt, int ldb, int M, 
     else return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: the no-store variant exists for tile_cfg 2 and 5 (4: -DAPH_EXPERIMENTS builds)");
     return aph_check_launch("aph_gemm_f16_ld");
   }
-  if (tile_cfg == 1) launch_gemm_cfg<GemmSmall>(A, lda, B, ldb, M, N, K, epi, st);
-  else if (tile_cfg == 2) launch_gemm_cfg<GemmBig>(A, lda, B, ldb, M, N, K, epi, st);
+  // the measurement-only families; everything else goes through gemm_f16_launch_cfg
 #ifdef APH_EXPERIMENTS
-  else if (tile_cfg == 4) launch_gemm8(A, lda, B, ldb, M, N, K, epi, st);
+  if (tile_cfg == 4) launch_gemm8(A, lda, B, ldb, M, N, K, epi, st);
 #else
-  else if (tile_cfg == 4) return aph_fail(APH_ERR_UNSUPPORTED, "aph_gemm_f16_ld: tile_cfg 4 (phased 256x256 kernel) exists in -DAPH_EXPERIMENTS builds only");
+  if (tile_cfg == 4) return aph_fail(APH_ERR_UNSUPPORTED, "aph_gemm_f16_ld: tile_cfg 4 (phased 256x256 kernel) exists in -DAPH_EXPERIMENTS builds only");
 #endif
-  else if (tile_cfg == 5) launch_gemm_ws_cfg<GemmWS>(A, lda, B, ldb, M, N, K, epi, st, nullptr);
-  else if (tile_cfg == 8 || tile_cfg == 9 || tile_cfg == 22 || tile_cfg == 24) {                // split-K (2 / 4 ways) of the 64x64 configuration, private workspace
-    static SplitKSpace sp;
-    const int splits = (tile_cfg == 8 || tile_cfg == 22) ? 2 : 4;
-    if (K / GEMM_BK < splits || (size_t)M * N > ((size_t)1 << 24)) return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: shape not usable with split-K");
-    if (!sp.ws) {
-      sp.ws_floats = (size_t)4 << 24;
-      if (hipMalloc((void**)&sp.ws, sp.ws_floats * sizeof(float)) != hipSuccess) return aph_fail(APH_ERR_HIP, "aph_gemm_f16_ld: split-K workspace");
-    }
-    if (tile_cfg >= 22) launch_gemm_splitk<GemmMidDeep8>(A, lda, B, ldb, M, N, K, epi, splits, sp, st);
-    else launch_gemm_splitk<GemmSmall>(A, lda, B, ldb, M, N, K, epi, splits, sp, st);
+  else if (tile_cfg == 22 || tile_cfg == 24) {                // split-K (2 / 4 ways) of the 128x128 configuration, private workspace
+    SplitKSpace* ws = nullptr;
+    if (const int rc = gemm_test_splitk_space(&ws)) return rc;
+    launch_gemm_splitk<GemmMidDeep8>(A, lda, B, ldb, M, N, K, epi, tile_cfg == 22 ? 2 : 4, *ws, st);
   }
-  else if (tile_cfg == 10) launch_gemm_cfg<GemmMidDeep8>(A, lda, B, ldb, M, N, K, epi, st);
   else if (tile_cfg == 11) launch_gemm_cfg<GemmPair>(A, lda, B, ldb, M, N, K, epi, st);
   else if (tile_cfg == 12) launch_gemm_cfg<GemmFat>(A, lda, B, ldb, M, N, K, epi, st);
-  else if (tile_cfg == 14) launch_gemm_sk<4>(A, lda, B, ldb, M, N, K, epi, st);
-  else if (tile_cfg == 15) launch_gemm_sk<3>(A, lda, B, ldb, M, N, K, epi, st);
 #ifdef APH_EXPERIMENTS
   else if (tile_cfg == 16) launch_gemm_ar<4, 8>(A, lda, B, ldb, M, N, K, epi, st);
   else if (tile_cfg == 17) launch_gemm_ar<4, 4>(A, lda, B, ldb, M, N, K, epi, st);
 #else
   else if (tile_cfg == 16 || tile_cfg == 17) return aph_fail(APH_ERR_UNSUPPORTED, "aph_gemm_f16_ld: tile_cfg 16 / 17 (A-resident kernel) exist in -DAPH_EXPERIMENTS builds only");
 #endif
-  else launch_gemm(A, lda, B, ldb, M, N, K, epi, st);
+  else if (const int rc = gemm_f16_launch_cfg(A, lda, B, ldb, M, N, K, epi, tile_cfg, nullptr, st)) return rc;
   return aph_check_launch("aph_gemm_f16_ld");
+  APH_CATCH
+}
+
+// One f16 GEMM with one of the ViT's epilogues (include/aphantasia_hip_test.h); tile_cfg: the product's families only
+int aph_gemm_f16_epi_test(const void* d_A, int lda, const void* d_Bt, int ldb, int M, int N, int K, void* d_out, int ldo, void* d_aux, const float* d_bias,
+                          const float* d_res, float scale, int epi_kind, int P, int T, int tile_cfg, float* d_ws, size_t ws_floats, int small_batch,
+                          void* stream_) {
+  APH_TRY
+  const bool cfg_ok = tile_cfg == 0 || tile_cfg == 1 || tile_cfg == 2 || tile_cfg == 5 || tile_cfg == 8 || tile_cfg == 9 || tile_cfg == 10 ||
+                      tile_cfg == 14 || tile_cfg == 15;
+  const bool need_ok = !((epi_kind == APH_EPI_RESIDUAL && (!d_bias || !d_res)) || (epi_kind == APH_EPI_GELU && (!d_aux || !d_bias)) ||
+                         (epi_kind == APH_EPI_GELU_BWD && !d_aux) || (epi_kind == APH_EPI_PATCH_EMBED && (!d_bias || P < 1 || T < P + 1 || M % P)));
+  if (!d_A || !d_Bt || !d_out || M < 1 || N < 128 || N % 128 || K < GEMM_BK || K % GEMM_BK || lda < K || ldb < K || (lda & 7) || (ldb & 7) ||
+      (epi_kind != APH_EPI_PATCH_EMBED && (ldo < N || (ldo & 7))) || epi_kind < APH_EPI_F32 || epi_kind > APH_EPI_PATCH_EMBED || !need_ok || !cfg_ok ||
+      !gemm_test_cfg_fits(tile_cfg, M, lda, N, ldb, K) || (d_ws && !ws_floats))
+    return aph_fail(APH_ERR_ARG, "aph_gemm_f16_epi_test: bad argument (epi_kind %d, tile_cfg %d, M=%d N=%d K=%d lda=%d ldb=%d ldo=%d)", epi_kind, tile_cfg,
+                    M, N, K, lda, ldb, ldo);
+  const half_t* A = (const half_t*)d_A;
+  const half_t* B = (const half_t*)d_Bt;
+  hipStream_t st = (hipStream_t)stream_;
+  SplitKSpace sp;
+  sp.ws = d_ws;
+  sp.ws_floats = d_ws ? ws_floats : 0;
+  sp.small_batch = small_batch != 0;
+  int rc = 0;
+  auto run = [&](auto epi) { rc = gemm_f16_launch_cfg(A, lda, B, ldb, M, N, K, epi, tile_cfg, &sp, st); };
+  switch (epi_kind) {
+    case APH_EPI_F32: run(EpiF32{(float*)d_out, ldo, scale}); break;
+    case APH_EPI_F16: run(EpiF16{(half_t*)d_out, ldo, d_bias}); break;
+    case APH_EPI_F16_SCALE: run(EpiF16Scale{(half_t*)d_out, ldo, scale}); break;
+    case APH_EPI_RESIDUAL: run(EpiResidual{(float*)d_out, d_res, ldo, d_bias}); break;
+    case APH_EPI_GELU: run(EpiGelu{(half_t*)d_aux, (half_t*)d_out, ldo, d_bias}); break;
+    case APH_EPI_GELU_BWD: run(EpiGeluBwd{(half_t*)d_out, (const half_t*)d_aux, ldo}); break;
+    default: run(EpiPatchEmbed{(float*)d_out, d_bias, N, P, T}); break;
+  }
+  if (rc) return rc;
+  return aph_check_launch("aph_gemm_f16_epi_test");
+  APH_CATCH
+}
+
+// The f16 path's LayerNorm launches alone, with the argument sets of vit.hip (include/aphantasia_hip_test.h)
+int aph_ln_test(int mode, int D, int M, int T, int xs, int res_T, int flags, const float* d_x, const float* d_g, const float* d_b, const void* d_dy,
+                const void* d_res, void* d_out, void* d_out2, const float* d_cls, const float* d_pos, float* d_x_fill, const float* d_x2,
+                const float* d_g2, const float* d_b2, void* stream_) {
+  APH_TRY
+  const int nv = D / 256, hilo = flags & 1, res_f16 = (flags >> 1) & 1;
+  bool ok = D % 256 == 0 && nv >= 1 && nv <= 4 && M >= 1 && T >= 1 && xs >= 1 && res_T >= 0 && d_x && d_g && (flags & ~3) == 0;
+  if (mode == 0) ok = ok && d_b && d_out && d_cls && d_pos && d_x_fill && xs == 1 && (!d_g2 == !d_b2) && (!d_g2 == !d_out2) && (!hilo || d_g2);
+  else if (mode == 1) ok = ok && d_b && d_out;
+  else if (mode == 2) ok = ok && d_dy && (d_out || d_out2) && (!d_x2 == !d_g2) && (!d_x2 || (d_out2 && !d_out && xs == 1)) && (!res_f16 || d_res);
+  else if (mode == 3) ok = ok && d_dy && d_out2 && xs == 1;
+  else ok = false;
+  if (!ok) return aph_fail(APH_ERR_ARG, "aph_ln_test: bad argument (mode %d, D=%d M=%d T=%d xs=%d flags=%d)", mode, D, M, T, xs, flags);
+  hipStream_t st = (hipStream_t)stream_;
+  if (mode == 0)
+    launch_ln_fwd<false, true>(nv, d_x, d_g, d_b, d_out, M, T, d_cls, d_pos, d_x_fill, st, 1, d_g2, d_b2, (half_t*)d_out2, hilo);
+  else if (mode == 1)
+    launch_ln_fwd<true, false>(nv, d_x, d_g, d_b, d_out, M, T, nullptr, nullptr, nullptr, st, xs, nullptr, nullptr, nullptr, hilo);
+  else if (mode == 2)
+    launch_ln_bwd<true, false>(nv, d_dy, d_x, d_g, d_res, (float*)d_out, (half_t*)d_out2, M, T, st, xs, res_T, d_x2, d_g2, res_f16);
+  else
+    launch_ln_bwd<false, true>(nv, d_dy, d_x, d_g, nullptr, nullptr, (half_t*)d_out2, M, T, st);
+  return aph_check_launch("aph_ln_test");
   APH_CATCH
 }
 

@@ -46,6 +46,43 @@ int aph_gemm_f16(const void* d_A, const void* d_Bt, int M, int N, int K, float* 
 int aph_gemm_f16_ld(const void* d_A, int lda, const void* d_Bt, int ldb, int M, int N, int K, float* d_C, int tile_cfg,
                     void* stream);
 
+/* One f16 GEMM with one of the ViT's epilogues (vit_gemm.h), an explicit tile configuration and explicit pitches (elements, multiples of 8):
+ * out = epilogue(A[M,K] * Bt[N,K]^T), N % 128 == 0, K % 64 == 0.  epi_kind (bias: N floats):
+ *    APH_EPI_F32          d_out f32 [M, ldo] = acc * scale                                   (patch-embedding dgrad, f32 gradient)
+ *    APH_EPI_F16          d_out f16 [M, ldo] = acc (+ d_bias if not NULL)                    (QKV; the dgrads without bias)
+ *    APH_EPI_F16_SCALE    d_out f16 [M, ldo] = acc * scale                                   (patch-embedding dgrad, f16 gradient)
+ *    APH_EPI_RESIDUAL     d_out f32 [M, ldo] = d_res [M, ldo] + acc + d_bias                  (out-proj, fc2)
+ *    APH_EPI_GELU         u = acc + d_bias: d_out f16 [M, ldo] = QuickGELU(u), d_aux f16 [M, ldo] = its derivative   (fc1)
+ *    APH_EPI_GELU_BWD     d_out f16 [M, ldo] = acc * d_aux (f16 [M, ldo])                    (fc2 dgrad)
+ *    APH_EPI_PATCH_EMBED  patch row m = s P + p -> d_out f32 row s T + 1 + p (pitch N) = acc + d_bias[(1 + p) N ...] (d_bias = pos [T, N];
+ *                         M % P == 0, T > P, ldo ignored; class rows s T are not written)
+ * tile_cfg: the product's families only -- 0 (automatic: launch_gemm with d_ws / ws_floats as the split-K workspace, or NULL, and small_batch as
+ * SplitKSpace::small_batch), 1, 2, 5, 8, 9, 10, 14, 15 as for aph_gemm_f16_ld; any other value, or a shape outside the family's limits, is
+ * rejected (APH_ERR_ARG). */
+#define APH_EPI_F32 0
+#define APH_EPI_F16 1
+#define APH_EPI_F16_SCALE 2
+#define APH_EPI_RESIDUAL 3
+#define APH_EPI_GELU 4
+#define APH_EPI_GELU_BWD 5
+#define APH_EPI_PATCH_EMBED 6
+int aph_gemm_f16_epi_test(const void* d_A, int lda, const void* d_Bt, int ldb, int M, int N, int K, void* d_out, int ldo, void* d_aux,
+                          const float* d_bias, const float* d_res, float scale, int epi_kind, int P, int T, int tile_cfg, float* d_ws,
+                          size_t ws_floats, int small_batch, void* stream);
+/* The f16 path's LayerNorm kernels (vit_ops.h) alone, D = 256 ... 1024 (a multiple of 256), rows of D floats unless said otherwise.
+ *   mode 0  ln_pre: d_out f32 [M, D] = LN(x; g, b); row t == 0 of every image (row % T == 0) is read as d_cls + d_pos[0 .. D) and also written
+ *           to d_x_fill.  d_g2 / d_b2 / d_out2 (all or none): the next LayerNorm fused behind it, d_out2 f16 = LN(out; g2, b2).  xs must be 1.
+ *   mode 1  d_out f16 [M, D] = LN(x; g, b), x row m at row m * xs (xs = T: class rows only)
+ *   mode 2  LayerNorm backward from f16 dy [M, D] (compact): x, res and the outputs at row m * xs; d_out f32 (or NULL), d_out2 f16 (or NULL);
+ *           d_res (or NULL) added on the rows m % res_T == 0 only when res_T > 0; flags & 2: d_res is f16 (it may alias d_out2).
+ *           d_x2 / d_g2: the previous LayerNorm's backward fused behind (input d_x2, gain d_g2): d_out2 then receives ITS input gradient in the
+ *           patch-row layout below and nothing else is written (d_out NULL, xs 1)
+ *   mode 3  LayerNorm backward from f32 dy [M, D] into d_out2 f16 in the patch-row layout: row s T + t -> s (T - 1) + t - 1, class rows dropped
+ * flags & 1 (modes 0, 1): hilo -- the f16 rows are [hi (D) | lo (D)] (the fused output of mode 0 only). */
+int aph_ln_test(int mode, int D, int M, int T, int xs, int res_T, int flags, const float* d_x, const float* d_g, const float* d_b, const void* d_dy,
+                const void* d_res, void* d_out, void* d_out2, const float* d_cls, const float* d_pos, float* d_x_fill, const float* d_x2,
+                const float* d_g2, const float* d_b2, void* stream);
+
 /* Crop / resize adjoint of aph_sample_bwd: 1 = always the per-pixel gather kernel (round 2), 0 = automatic (the separable row-block kernel
  * on frames without wrap padding).  Process-wide, returns the previous value.  (No environment variable changes which kernels the library
  * runs: every switch here is an explicit call.) */

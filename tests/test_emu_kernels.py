@@ -12,6 +12,7 @@ import torch
 
 from aphantasia_amd import _ffi
 import kernel_checks as K
+import vit_component_checks as V
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), 'emu'))
 
@@ -264,3 +265,49 @@ def test_sampler_small_image_and_random_geometries(emu, monkeypatch):
             K.check_sampler_adjoint(emu, 'cpu', align, _ffi.APH_OUT_PATCH_F16, H=72, W=H, S=4, size=8, patch=8)
     monkeypatch.setattr('aphantasia_amd.transforms._EXACT_ZERO_ROT', True)       # (the oracle resamples 0-degree cuts too)
     K.check_sampler_fuzz(emu, 'cpu', seed=11, n=14)
+
+
+# ---- f16 GEMM epilogues and LayerNorm variants against fp64 (vit_component_checks.py), every product kernel family, explicit tile_cfg:
+# (M, N, K, lda, ldb) -- a single partial tile, ragged last row tiles, 2 / 4 column tiles, the family's smallest K, padded pitches
+EPI_FAMILIES = {
+    1: [(50, 128, 64, None, None), (129, 256, 128, 136, 192)],
+    2: [(257, 128, 64, 72, 128)],
+    10: [(129, 256, 128, 192, 136)],
+    5: [(50, 128, 64, None, None), (257, 256, 128, 136, 192)],       # (2 x 2 tiles on the interpreter's 3 persistent workgroups)
+    8: [(50, 128, 128, 136, None)],
+    9: [(65, 256, 256, None, 320)],
+    14: [(50, 128, 256, 264, None), (129, 128, 256, None, 320)],
+    15: [(129, 128, 256, 320, None)],
+}
+EPI_KINDS = {'f32_scale': dict(kind=V.EPI_F32, scale=0.37), 'f16_bias': dict(kind=V.EPI_F16), 'f16': dict(kind=V.EPI_F16, bias=False),
+             'f16_scale': dict(kind=V.EPI_F16_SCALE, scale=1.37), 'residual': dict(kind=V.EPI_RESIDUAL), 'gelu': dict(kind=V.EPI_GELU),
+             'gelu_bwd': dict(kind=V.EPI_GELU_BWD), 'patch_embed': dict(kind=V.EPI_PATCH_EMBED)}
+
+
+@pytest.mark.parametrize('epi', list(EPI_KINDS))
+@pytest.mark.parametrize('tile_cfg', list(EPI_FAMILIES))
+def test_gemm_epilogue_vs_fp64(emu, tile_cfg, epi):
+    for (M, N, Kd, lda, ldb) in EPI_FAMILIES[tile_cfg]:
+        V.check_gemm_epilogue(emu, 'cpu', tile_cfg=tile_cfg, M=M, N=N, K=Kd, lda=lda, ldb=ldb, ws_residual=tile_cfg == 5, mfma_k=1,
+                              **EPI_KINDS[epi])
+
+
+@pytest.mark.parametrize('epi', list(EPI_KINDS))
+def test_gemm_epilogue_automatic_split_k(emu, epi):
+    """tile_cfg 0 with a workspace and a batch that is not small: launch_gemm's choose_splits takes K = 1536 four ways (two-pass split-K,
+    the reduce kernel applies the epilogue)"""
+    V.check_gemm_epilogue(emu, 'cpu', tile_cfg=0, M=5, N=128, K=1536, ldb=1600, ws_floats=1 << 16, small_batch=0, **EPI_KINDS[epi])
+
+
+@pytest.mark.parametrize('epi', ['residual', 'f16'])
+@pytest.mark.parametrize('tile_cfg', [0, 14])
+def test_gemm_epilogue_class_rows(emu, tile_cfg, epi):
+    """the last block's GEMMs on its class rows only: lda = ldo = T * D, M = cuts (T = 5, D = 256)"""
+    V.check_gemm_epilogue(emu, 'cpu', tile_cfg=tile_cfg, M=3, N=256, K=256, lda=5 * 256, ldo=5 * 256, ws_floats=1 << 16 if tile_cfg == 0 else 0,
+                          small_batch=0, **EPI_KINDS[epi])
+
+
+@pytest.mark.parametrize('D', [256, 512, 768])
+@pytest.mark.parametrize('case', V.LN_CASES)
+def test_layernorm_vs_fp64(emu, case, D):
+    V.check_layernorm(emu, 'cpu', case, D)

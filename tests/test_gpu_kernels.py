@@ -7,6 +7,7 @@ import torch
 
 from aphantasia_amd import _ffi, ops
 import kernel_checks as K
+import vit_component_checks as V
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -323,3 +324,64 @@ def test_frame_affine():
 
 def test_adam_guard():
     K.check_adam_guard(None, DEV)
+
+
+# ---- f16 GEMM epilogues and LayerNorm variants against fp64 (vit_component_checks.py) at ViT-B/32 shapes, every product kernel family.
+# Epilogue -> (M, N, K) of the ViT launch that uses it, at 49 cuts (2450 token rows, 2401 patch rows) or 24 cuts (1200 / 1176).
+EPI_KINDS = {'f32_scale': dict(kind=V.EPI_F32, scale=0.37), 'f16_bias': dict(kind=V.EPI_F16), 'f16': dict(kind=V.EPI_F16, bias=False),
+             'f16_scale': dict(kind=V.EPI_F16_SCALE, scale=1.37), 'residual': dict(kind=V.EPI_RESIDUAL), 'gelu': dict(kind=V.EPI_GELU),
+             'gelu_bwd': dict(kind=V.EPI_GELU_BWD), 'patch_embed': dict(kind=V.EPI_PATCH_EMBED)}
+VIT_SHAPES = {'f32_scale': (2401, 3072, 768), 'f16_scale': (2401, 3072, 768),          # patch-embedding dgrad
+              'f16_bias': (2450, 2304, 768), 'f16': (2450, 768, 3072),                  # QKV; fc1 dgrad
+              'residual': (2450, 768, 3072), 'gelu': (2450, 3072, 768),                 # fc2; fc1
+              'gelu_bwd': (2450, 3072, 768), 'patch_embed': (2401, 768, 3072)}          # fc2 dgrad; patch embedding (P = 49, T = 50)
+
+
+def _vit_shape(epi, cuts):
+    """(M, N, K, patch geometry) of the epilogue's ViT launch at `cuts` cuts: 50 token rows or 49 patch rows per cut"""
+    M, N, Kd = VIT_SHAPES[epi]
+    return cuts * (49 if M == 2401 else 50), N, Kd, (dict(P=49, T=50) if epi == 'patch_embed' else {})
+
+
+@pytest.mark.parametrize('epi', list(EPI_KINDS))
+@pytest.mark.parametrize('tile_cfg', [2, 5, 1, 10])
+def test_gemm_epilogue_vs_fp64_vit_shapes(tile_cfg, epi):
+    """the ring kernels (2: 256x128, 1: 64x64, 10: 128x128) and the wave-specialised kernel (5) with every epilogue; the 64x64 and 128x128
+    configurations at 24 cuts, one launch per family with padded A / Bt pitches"""
+    M, N, Kd, pt = _vit_shape(epi, 49 if tile_cfg in (2, 5) else 24)
+    pad = dict(lda=Kd + 8, ldb=Kd + 64) if epi in ('residual', 'gelu') else {}
+    st = V.check_gemm_epilogue(None, DEV, tile_cfg=tile_cfg, M=M, N=N, K=Kd, ws_residual=tile_cfg == 5, **pad, **pt, **EPI_KINDS[epi])
+    if epi == 'residual':
+        print('tile_cfg %d residual: worst err / (e_acc + 2 ulp) %.3f' % (tile_cfg, st['ratio']))
+
+
+@pytest.mark.parametrize('epi', list(EPI_KINDS))
+@pytest.mark.parametrize('tile_cfg', [8, 9, 14, 15])
+def test_gemm_epilogue_vs_fp64_small_m(tile_cfg, epi):
+    """the two-pass split-K (8 / 9) and the register-staged split-K (14 / 15) at small M (ragged 64-row tiles), K = 768 / 3072"""
+    _, N, Kd, pt = _vit_shape(epi, 1)
+    M = (98 if tile_cfg >= 14 else 294) if epi == 'patch_embed' else (129 if tile_cfg >= 14 else 300)
+    V.check_gemm_epilogue(None, DEV, tile_cfg=tile_cfg, M=M, N=N, K=Kd, **pt, **EPI_KINDS[epi])
+
+
+@pytest.mark.parametrize('epi,Kd', [('residual', 768), ('residual', 3072), ('f16', 768)])
+def test_gemm_epilogue_class_rows(epi, Kd):
+    """the last block's GEMMs on its class rows: lda = ldo = 50 * 768, M = 49 cuts -- automatic choice with the ViT's split-K workspace
+    (a batch that is not small: choose_splits), and the register-staged kernel"""
+    for tile_cfg, ws in ((0, 1 << 22), (14, 0)):
+        V.check_gemm_epilogue(None, DEV, tile_cfg=tile_cfg, M=49, N=768, K=Kd, lda=50 * 768, ldo=50 * 768, ws_floats=ws, small_batch=0,
+                              **EPI_KINDS[epi])
+
+
+def test_gemm_epilogue_residual_at_stress_magnitude():
+    """fc2 with residuals 100x the product (the stress weights' outliers): the ring kernel meets e_acc + 2 ulp of |res + acc + bias|; the
+    wave-specialised kernel, which starts its accumulators at res + bias, its derived (K/32 + 2) ulp bound (vit_component_checks.py)"""
+    for tile_cfg in (2, 5):
+        st = V.check_gemm_epilogue(None, DEV, V.EPI_RESIDUAL, tile_cfg, 2450, 768, 3072, res_mag=100.0, ws_residual=tile_cfg == 5, seed=3)
+        print('tile_cfg %d residual x100: worst err / (e_acc + 2 ulp) %.3f' % (tile_cfg, st['ratio']))
+
+
+@pytest.mark.parametrize('D', [256, 512, 768])
+@pytest.mark.parametrize('case', V.LN_CASES)
+def test_layernorm_vs_fp64(case, D):
+    V.check_layernorm(None, DEV, case, D, S=49 if D == 768 else 3, T=50 if D == 768 else 5)

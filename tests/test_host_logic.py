@@ -196,12 +196,37 @@ def test_error_convention_on_bad_arguments(product_lib):
         'aph_grid_warp': lambda: L.aph_grid_warp(null, null, 3, 8, 8, ctypes.c_float(0.3), ctypes.c_float(0.0), ctypes.c_float(0.0), ctypes.c_float(0.5),
                                                  ctypes.c_float(0.05), null, null, null),
         'aph_attn_test': lambda: L.aph_attn_test(null, null, null, null, null, null, 1, 50, 12, 0, null),
+        'aph_gemm_f16_epi_test': lambda: L.aph_gemm_f16_epi_test(null, 64, null, 64, 1, 128, 64, null, 128, null, null, null, ctypes.c_float(1.0), 1,
+                                                                 0, 0, 0, null, ctypes.c_size_t(0), 1, null),
+        'aph_ln_test': lambda: L.aph_ln_test(1, 256, 1, 1, 1, 0, 0, null, null, null, null, null, null, null, null, null, null, null, null, null, null),
         'aph_allreduce_f32': lambda: L.aph_allreduce_f32(null, null, ctypes.c_size_t(1), null),
     }
     for name, call in cases.items():
         rc = call()
         assert rc < 0, name
         assert product_lib.last_error(), name
+
+
+def test_gemm_epi_test_refuses_what_the_product_does_not_run(product_lib):
+    """aph_gemm_f16_epi_test takes the product's kernel families only (tile_cfg 0, 1, 2, 5, 8, 9, 10, 14, 15) within their shape limits, and
+    the buffers its epilogue needs; everything else is refused before any device work (the pointers below are never dereferenced)"""
+    import ctypes
+    L = product_lib.cdll
+    p = ctypes.c_void_p(4096)
+
+    def call(tile_cfg=1, kind=1, M=64, N=128, K=64, ldo=128, aux=p, bias=p, res=p, P=0, T=0):
+        return L.aph_gemm_f16_epi_test(p, K, p, K, M, N, K, p, ldo, aux, bias, res, ctypes.c_float(1.0), kind, P, T, tile_cfg, None,
+                                       ctypes.c_size_t(0), 1, None)
+    for cfg in (3, 4, 6, 7, 11, 12, 13, 16, 17, 22, 24, 0x102, -1):
+        assert call(tile_cfg=cfg) == -1 and 'tile_cfg' in product_lib.last_error(), cfg
+    assert call(tile_cfg=14, K=512) == -1                         # register-staged: K in {256, 768, 1024, 2304, 3072}
+    assert call(tile_cfg=9, K=192) == -1                          # split-K x4 needs 4 k-tiles
+    assert call(tile_cfg=5, N=4224) == -1                         # wave-specialised: N <= 4096 (the bias stays in LDS)
+    assert call(ldo=120) == -1 and call(ldo=132) == -1            # ldo >= N, a multiple of 8
+    assert call(kind=7) == -1 and call(kind=-1) == -1
+    assert call(kind=3, res=None) == -1 and call(kind=3, bias=None) == -1
+    assert call(kind=4, aux=None) == -1 and call(kind=5, aux=None) == -1
+    assert call(kind=6, P=64, T=64) == -1 and call(kind=6, P=48, T=49) == -1      # T > P, M % P == 0
 
 
 def _uid_worker(rank, world, port, mode, q):
