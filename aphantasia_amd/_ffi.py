@@ -106,16 +106,6 @@ _PROTOTYPES = {
 
 EXPORTS = tuple(_PROTOTYPES)
 
-# hooks of a -DAPH_EXPERIMENTS build (include/aphantasia_hip_experiments.h): bound when the loaded library has them
-_EXPERIMENT_PROTOTYPES = {
-    'aph_vit_set_fused_max_rows': (c_int, [c_int]),
-    'aph_vit_set_fused_attn': (c_int, [c_int]),
-    'aph_gemm_pack_frag': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    'aph_attn_set_bwd_one': (c_int, [c_int]),
-    'aph_attn_set_ablate': (c_int, [c_int]),
-}
-
-
 class Library:
     """A loaded C-ABI library with checked calls: `lib.call('aph_x', ...)` raises RuntimeError with
     aph_last_error() on a negative return code."""
@@ -132,12 +122,6 @@ class Library:
             fn = getattr(self.cdll, name)     # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args
-        self.experiments = all(hasattr(self.cdll, n) for n in _EXPERIMENT_PROTOTYPES)
-        if self.experiments:
-            for name, (res, args) in _EXPERIMENT_PROTOTYPES.items():
-                fn = getattr(self.cdll, name)
-                fn.restype = res
-                fn.argtypes = args
 
     def last_error(self):
         return (self.cdll.aph_last_error() or b'').decode(errors='replace')

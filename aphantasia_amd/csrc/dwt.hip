@@ -494,15 +494,6 @@ void launch_idwt_coarse_adjoint(const IdwtLevels& lv, int C, size_t smem, hipStr
 // filter lengths the coarse-tail kernels are instantiated for (fully unrolled filter loops)
 inline bool idwt_coarse_length(int L) { return L == 2 || L == 4 || L == 6 || L == 8; }
 constexpr size_t kCoarseSmemMax = 150 * 1024;
-// (-DAPH_EXPERIMENTS builds only: APH_IDWT_COARSE=0 in the environment = one launch per level throughout, for A/B runs)
-inline bool idwt_coarse_enabled() {
-#ifdef APH_EXPERIMENTS
-  static const bool on = [] { const char* e = getenv("APH_IDWT_COARSE"); return !(e && e[0] == '0'); }();
-  return on;
-#else
-  return true;
-#endif
-}
 
 void idwt_level_fwd(const float* d_ll, int ll_h, int ll_w, const float* d_highs, int h, int w, int C, const float* d_g0,
                     const float* d_g1, int L, float hscale, float* d_out, hipStream_t st) {
@@ -573,7 +564,7 @@ int idwt_check_levels(const char* who, const int* hs, const int* ws, int J, int 
 }
 // number of levels, counted from the coarsest, that the coarse-tail kernel takes (0: none -- it needs at least two to pay)
 inline int idwt_coarse_count(const int* hs, const int* ws, int J, int L) {
-  if (!idwt_coarse_enabled() || !idwt_coarse_length(L)) return 0;
+  if (!idwt_coarse_length(L)) return 0;
   int n = 0, hsum = 0;
   for (int j = J - 1; j >= 0 && n < DC_MAX_LEVELS; --j, ++n) {
     int llh, llw;

@@ -538,6 +538,7 @@ template <int OUT, int RBQ, int CPT>
 __global__ __launch_bounds__(768) void crop_adjoint_rows_kernel(const void* __restrict__ gout, float gscale, const int* __restrict__ table,
                                                                  float* __restrict__ grgb, Geom g, const AdjEntry* __restrict__ tab, int maxcs,
                                                                  int RB, int NBC, int dbg, int XW, int center_out) {
+  // dbg: bit 0 skips the column pass, bit 1 the row pass (a round-6 ablation, profiles/r06_crop_adjoint_sweep.txt); the launcher passes 0.
   // [r4] XW: columns per workgroup; blockIdx.z selects the column segment [x0, x0 + XW) (frames wider than 768 threads x 3 columns: the
   // 3840-wide C4 frame is two segments; a segment culls the cuts that do not reach it)
   constexpr int RBP = RBQ * 4, MAXV = 512;
@@ -1207,42 +1208,19 @@ int launch_crop_adjoint(const void* gout, float gscale, const int* table, float*
     rb = rb < 4 ? 4 : (rb > 16 ? 16 : rb);
     if (ov.rb > 0) rb = ov.rb;
     int rbq = rb <= 12 ? 3 : 4;
-#if defined(APH_EXPERIMENTS) && !defined(APH_EMU)
-    if (ov.rb > 0) rbq = (rb + 3) / 4;
-#endif
     const int rbp = rbq * 4;
     int nbc = ov.nbc > 0 && ov.nbc <= ADJ_NBC ? ov.nbc : ADJ_NBC;
     auto lds = [&](int n) { return (size_t)n * g.size * rbp * 4 + 2 * (size_t)n * rbq * 8 * sizeof(QuadRow) + 2 * (size_t)n * 16 + 512 * 16 + 16; };
     while (nbc > 1 && lds(nbc) > 150 * 1024) --nbc;
     if (lds(nbc) <= 150 * 1024) {
       const dim3 rgrid((g.H + rb - 1) / rb, 3, nseg);
-#ifdef APH_EXPERIMENTS      /* ablation hook (1 = no column pass, 2 = no row pass: WRONG gradients) -- only in a -DAPH_EXPERIMENTS build, never in the product library */
-      static const int dbg = [] { const char* e = getenv("APH_SAMPLER_DBG"); return e ? atoi(e) : 0; }();
-#else
-      constexpr int dbg = 0;
-#endif
       const size_t smem = lds(nbc);
       const int center_out = ov.order >= 0 ? ov.order : ((int)(rgrid.x * 3 * nseg) > gemm_like_cu_count() ? 1 : 0);
 #define APH_ADJ_ROWS(RBQ, CPT)                                                                                                              \
   do {                                                                                                                                       \
     APH_ALLOW_SMEM((crop_adjoint_rows_kernel<OUT, RBQ, CPT>), 150 * 1024);                                                                   \
-    APH_LAUNCH((crop_adjoint_rows_kernel<OUT, RBQ, CPT>), rgrid, dim3(nthr), smem, st, gout, gscale, table, grgb, g, (const AdjEntry*)tab, maxcs, rb, nbc, dbg, xw, center_out); \
+    APH_LAUNCH((crop_adjoint_rows_kernel<OUT, RBQ, CPT>), rgrid, dim3(nthr), smem, st, gout, gscale, table, grgb, g, (const AdjEntry*)tab, maxcs, rb, nbc, /*dbg*/ 0, xw, center_out); \
   } while (0)
-#if defined(APH_EXPERIMENTS) && !defined(APH_EMU)       /* every (rows, columns per thread) shape, for the launch-shape sweep of tools/exp/crop_adjoint_sweep.py (GPU only: the interpreter build skips them) */
-      if (rbq == 1 && cpt == 1) APH_ADJ_ROWS(1, 1);
-      else if (rbq == 1 && cpt == 2) APH_ADJ_ROWS(1, 2);
-      else if (rbq == 1) APH_ADJ_ROWS(1, 3);
-      else if (rbq == 2 && cpt == 1) APH_ADJ_ROWS(2, 1);
-      else if (rbq == 2 && cpt == 2) APH_ADJ_ROWS(2, 2);
-      else if (rbq == 2) APH_ADJ_ROWS(2, 3);
-      else if (rbq == 3 && cpt == 1) APH_ADJ_ROWS(3, 1);
-      else if (rbq == 4 && cpt == 1) APH_ADJ_ROWS(4, 1);
-      else if (rbq == 5 && cpt == 2) APH_ADJ_ROWS(5, 2);
-      else if (rbq == 5) APH_ADJ_ROWS(5, 3);
-      else if (rbq == 6 && cpt == 2) APH_ADJ_ROWS(6, 2);
-      else if (rbq >= 6) APH_ADJ_ROWS(6, 3);
-      else
-#endif
       if (rbq == 3 && cpt == 2) APH_ADJ_ROWS(3, 2);
       else if (rbq == 3) APH_ADJ_ROWS(3, 3);
       else if (cpt == 2) APH_ADJ_ROWS(4, 2);
@@ -1260,7 +1238,7 @@ int launch_crop_adjoint(const void* gout, float gscale, const int* table, float*
 extern "C" {
 
 // test / measurement hook: launch shape of the separable crop adjoint (rows per workgroup, columns per thread, cuts per batch, column
-// segments, row-block order 0 = top-down / 1 = centre-out); 0 (order: -1) = automatic.  rb beyond the shipped kernel shapes needs a -DAPH_EXPERIMENTS build.
+// segments, row-block order 0 = top-down / 1 = centre-out); 0 (order: -1) = automatic.  The kernel is instantiated for 12 or 16 accumulator rows x 2 or 3 columns per thread.
 int aph_crop_adjoint_set_shape(int rb, int cpt, int nbc, int nseg, int order) {
   CropAdjointShape& v = crop_adjoint_shape();
   v.rb = rb; v.cpt = cpt; v.nbc = nbc; v.nseg = nseg; v.order = order;

@@ -19,9 +19,6 @@
 #include "vit_attn.h"
 #include "vit_gemm_f32.h"
 #include "vit_attn_f32.h"
-#ifdef APH_EXPERIMENTS
-#include "vit_block.h"
-#endif
 
 using namespace aph;
 
@@ -52,8 +49,7 @@ struct aph_vit {
   std::vector<Layer> layers;
   float *x0 = nullptr, *x_last = nullptr;
   half_t *h = nullptr, *gact = nullptr;
-  float *dx = nullptr, *dx2 = nullptr;      // fp32 residual-stream gradient (dx2: the second buffer of the fused backward's hand-over)
-  float* delta = nullptr;              // attention backward row dots dO_i . O_i (T > 64 path)
+  float* dx = nullptr;                 // fp32 residual-stream gradient
   half_t *dx16 = nullptr, *du = nullptr, *dh = nullptr, *datt = nullptr, *dqkv = nullptr, *dx0_16 = nullptr;
   SplitKSpace sk;                      // split-K partials of the small-M GEMMs (per-rank shards, class-row GEMMs)
   char* arena = nullptr;
@@ -148,10 +144,6 @@ void carve(aph_vit* v, char* base, size_t* total) {
   v->x0 = c.take<float>(Mx * D); v->x_last = c.take<float>(Mx * D);
   v->h = c.take<half_t>(Mx * 2 * D); v->gact = c.take<half_t>(Mx * 4 * D);      // h: [hi | lo] rows in the split-precision forward
   v->dx = c.take<float>(Mx * D);
-#ifdef APH_EXPERIMENTS       // scratch of measured-and-not-adopted paths only: the fused backward's hand-over buffer, the two-kernel attention backward's row dots
-  v->dx2 = c.take<float>(Mx * D);
-  v->delta = c.take<float>((size_t)v->max_batch * v->heads * T);
-#endif
   v->dx16 = c.take<half_t>(Mx * D); v->du = c.take<half_t>(Mx * 4 * D); v->dh = c.take<half_t>(Mx * D);
   v->datt = c.take<half_t>(Mx * D); v->dqkv = c.take<half_t>(Mx * 3 * D); v->dx0_16 = c.take<half_t>(Mx * D);
   v->sk.ws_floats = (size_t)256 * GemmSmall::BM * GemmSmall::BN;       // choose_splits keeps tiles * splits <= 256
@@ -241,57 +233,6 @@ void vgemm32(aph_vit* v, const float* A, int lda, const float* Bt, int ldb, int 
   vtimed(v, 2.0 * M * N * K, st, [&] { launch_gemm_f32(A, lda, Bt, ldb, M, N, K, epi, st, &v->f32sp, a_rowP); });
 }
 
-#ifdef APH_EXPERIMENTS
-// Fused block kernels (vit_block.h) for short sequences: used while the batch has at most this many token rows (0 = never).  Above it the
-// one-launch-per-operator path with the wave-specialised GEMM is the faster one (measured crossover: DESIGN.md section 4).
-#ifndef APH_VIT_FUSED_MAX_ROWS_DEFAULT
-#define APH_VIT_FUSED_MAX_ROWS_DEFAULT 0
-#endif
-int g_fused_max_rows = APH_VIT_FUSED_MAX_ROWS_DEFAULT;
-inline bool vit_fused(const aph_vit* v, int S) { return v->T <= AT_T && v->D <= 1024 && (long long)S * v->T <= g_fused_max_rows; }
-// the (cut, head) kernel with the attention behind the QKV GEMM holds 120 KiB of LDS -- one workgroup per CU -- so it only pays while all
-// S x heads workgroups run at once (288 of them on 256 CUs take two rounds: 33 against 21 us at 24 cuts); otherwise LayerNorm + QKV go
-// through the flat-row kernel and the attention stays a launch of its own.  0 = never, 1 = automatic, 2 = always (tests).
-int g_fused_attn = 1;
-inline bool vit_fused_attn(const aph_vit* v, int S) { return g_fused_attn == 2 || (g_fused_attn == 1 && S * v->heads <= gemm_persistent_wgs()); }
-
-void launch_qkv_attn(aph_vit* v, const Layer& l, int S, hipStream_t st) {
-  const int nv = v->D / 256;
-  auto go = [&](auto tag) {
-    constexpr int NV = decltype(tag)::value;
-    launch_blk_qkv_attn<NV, 4>(l.x_in, l.ln1_g, l.ln1_b, l.w_qkv, l.b_qkv, l.qkv, l.att, l.lse, S, v->T, v->heads, st);
-  };
-  switch (nv) {
-    case 1: go(std::integral_constant<int, 1>{}); break;
-    case 2: go(std::integral_constant<int, 2>{}); break;
-    case 3: go(std::integral_constant<int, 3>{}); break;
-    default: go(std::integral_constant<int, 4>{}); break;
-  }
-}
-template <class Epi>
-void launch_lnbwd_gemm(aph_vit* v, const half_t* dy, const float* x, const float* g, const float* res, float* out32, int res_T, int M, const half_t* Wt,
-                       int N, Epi epi, hipStream_t st) {
-  switch (v->D / 256) {
-    case 1: launch_blk_lnbwd_gemm<1, 4>(dy, x, g, res, out32, res_T, M, Wt, N, epi, st); break;
-    case 2: launch_blk_lnbwd_gemm<2, 4>(dy, x, g, res, out32, res_T, M, Wt, N, epi, st); break;
-    case 3: launch_blk_lnbwd_gemm<3, 4>(dy, x, g, res, out32, res_T, M, Wt, N, epi, st); break;
-    default: launch_blk_lnbwd_gemm<4, 4>(dy, x, g, res, out32, res_T, M, Wt, N, epi, st); break;
-  }
-}
-template <class Epi>
-void launch_ln_gemm(aph_vit* v, const float* x, int xs, int M, const float* g, const float* b, const half_t* Wt, int N, Epi epi, hipStream_t st) {
-  switch (v->D / 256) {
-    case 1: launch_blk_ln_gemm<1, 4>(x, xs, M, g, b, Wt, N, epi, st); break;
-    case 2: launch_blk_ln_gemm<2, 4>(x, xs, M, g, b, Wt, N, epi, st); break;
-    case 3: launch_blk_ln_gemm<3, 4>(x, xs, M, g, b, Wt, N, epi, st); break;
-    default: launch_blk_ln_gemm<4, 4>(x, xs, M, g, b, Wt, N, epi, st); break;
-  }
-}
-
-#else
-inline bool vit_fused(const aph_vit*, int) { return false; }
-#endif
-
 // g2 / b2 / out2: the next LayerNorm of the same rows fused behind this one (ln_fwd_kernel)
 template <bool OUT_F16, bool CLS>
 void launch_ln_fwd(int nv, const float* x, const float* g, const float* b, void* out, int M, int T, const float* cls,
@@ -326,7 +267,7 @@ int g_grad_stream_f16 = 0;
 // attention launches: T <= 64 one-tile kernels, 64 < T <= 256 the blocked kernels (NB = ceil(T / 64))
 struct AttnArgs {
   const half_t* qkv; half_t* att; float* lse;        // forward: qkv -> att, lse
-  const half_t* datt; float* delta; half_t* dqkv;    // backward: (qkv, att, lse, datt) -> dqkv; delta [S*heads*T] scratch for T > 64
+  const half_t* datt; half_t* dqkv;                  // backward: (qkv, att, lse, datt) -> dqkv
   int S, T, heads;
 };
 template <int NB>
@@ -335,32 +276,13 @@ void launch_attn_fwd_g(const AttnArgs& a, hipStream_t st) {
   APH_ALLOW_SMEM((attn_fwd_mfma_g_kernel<NB>), smem);
   APH_LAUNCH((attn_fwd_mfma_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem, st, a.qkv, a.att, a.lse, a.T, a.heads);
 }
-// blocked backward (64 < T <= 256): one kernel, P and dS formed once (attn_bwd_one_g_kernel); -DAPH_EXPERIMENTS builds can switch back to
-// the dQ + dK/dV kernel pair it superseded (aph_attn_set_bwd_one(0))
-#ifdef APH_EXPERIMENTS
-int g_attn_bwd_one = 1;
-#endif
+// blocked backward (64 < T <= 256): one kernel, P and dS formed once (attn_bwd_one_g_kernel)
 template <int NB>
 void launch_attn_bwd_g(const AttnArgs& a, hipStream_t st) {
-#ifdef APH_EXPERIMENTS
-  if (g_attn_bwd_one)
-#endif
-  {
-    constexpr size_t smem = (size_t)(4 + 2 * NB) * 8192 + 2 * 64 * sizeof(float);
-    APH_ALLOW_SMEM((attn_bwd_one_g_kernel<NB>), smem);
-    APH_LAUNCH((attn_bwd_one_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem, st, a.qkv, (const half_t*)a.att, a.datt, (const float*)a.lse, a.dqkv,
-               a.T, a.heads);
-    return;
-  }
-#ifdef APH_EXPERIMENTS
-  constexpr size_t smem_q = (size_t)3 * NB * 8192, smem_kv = (size_t)4 * NB * 8192 + 2 * NB * 64 * sizeof(float);
-  APH_ALLOW_SMEM((attn_bwd_dq_g_kernel<NB>), smem_q);
-  APH_ALLOW_SMEM((attn_bwd_dkv_g_kernel<NB>), smem_kv);
-  APH_LAUNCH((attn_bwd_dq_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem_q, st, a.qkv, (const half_t*)a.att, a.datt, (const float*)a.lse, a.delta,
-             a.dqkv, a.T, a.heads);
-  APH_LAUNCH((attn_bwd_dkv_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem_kv, st, a.qkv, a.datt, (const float*)a.lse, (const float*)a.delta,
-             a.dqkv, a.T, a.heads);
-#endif
+  constexpr size_t smem = (size_t)(4 + 2 * NB) * 8192 + 2 * 64 * sizeof(float);
+  APH_ALLOW_SMEM((attn_bwd_one_g_kernel<NB>), smem);
+  APH_LAUNCH((attn_bwd_one_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem, st, a.qkv, (const half_t*)a.att, a.datt, (const float*)a.lse, a.dqkv,
+             a.T, a.heads);
 }
 void launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   const int T = a.T;
@@ -388,18 +310,10 @@ inline int attn_bwd_wgs(int items) {
   return items < w ? items : w;
 #endif
 }
-#ifdef APH_EXPERIMENTS
-int g_attn_ablate = 0;       // aph_attn_set_ablate: measurement variants of the T <= 56 backward (WRONG results)
-#endif
 void launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
   const int T = a.T, items = a.S * a.heads;
   if (T <= AT_T)       // (the split dQ / dKdV kernels with NB = 1 were measured slower here: 7.62 vs 7.35 ms per C2 step)
   {
-#ifdef APH_EXPERIMENTS
-    if (T <= AT_RB && g_attn_ablate == 1) { APH_LAUNCH((attn_bwd_mfma_kernel<AT_RB, 1>), dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items); return; }
-    if (T <= AT_RB && g_attn_ablate == 2) { APH_LAUNCH((attn_bwd_mfma_kernel<AT_RB, 2>), dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items); return; }
-    if (T <= AT_RB && g_attn_ablate == 3) { APH_LAUNCH((attn_bwd_mfma_kernel<AT_RB, 3>), dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items); return; }
-#endif
     if (T <= AT_RB)
       APH_LAUNCH(attn_bwd_mfma_kernel<AT_RB>, dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items);
     else
@@ -410,7 +324,7 @@ void launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
   else launch_attn_bwd_g<4>(a, st);
 }
 inline AttnArgs attn_args(aph_vit* v, const Layer& l, int S) {
-  return AttnArgs{(const half_t*)l.qkv, l.att, l.lse, (const half_t*)v->datt, v->delta, v->dqkv, S, v->T, v->heads};
+  return AttnArgs{(const half_t*)l.qkv, l.att, l.lse, (const half_t*)v->datt, v->dqkv, S, v->T, v->heads};
 }
 
 }  // namespace
@@ -452,8 +366,8 @@ static int gemm_f16_launch_cfg(const half_t* A, int lda, const half_t* B, int ld
 }
 // the shape limits of tile_cfg 5, 8 / 9 / 22 / 24 and 14 / 15 (false: refuse)
 static bool gemm_test_cfg_fits(int tile_cfg, int M, int lda, int N, int ldb, int K) {
-  if (tile_cfg == 5) return gemm8_addressable(M, lda, N, ldb) && N <= GemmWS::BIAS_MAX;
-  if (tile_cfg == 14 || tile_cfg == 15) return gemm8_addressable(M, lda, N, ldb) && gemm_sk_fits(N, K);
+  if (tile_cfg == 5) return gemm_addressable32(M, lda, N, ldb) && N <= GemmWS::BIAS_MAX;
+  if (tile_cfg == 14 || tile_cfg == 15) return gemm_addressable32(M, lda, N, ldb) && gemm_sk_fits(N, K);
   if (tile_cfg == 8 || tile_cfg == 9 || tile_cfg == 22 || tile_cfg == 24)
     return K / GEMM_BK >= ((tile_cfg == 8 || tile_cfg == 22) ? 2 : 4) && (size_t)M * N <= ((size_t)1 << 24);
   return true;
@@ -632,56 +546,38 @@ static int vit_forward_impl(aph_vit* v, const void* d_patches, int S, float* d_e
   v->sk.small_batch = M <= 128;   // see gemm_rs_mode(): the split-K small-M kernel only when the whole batch is small
   vgemm(v, (const half_t*)d_patches, kx * v->Kp, hilo ? v->w_patch2 : v->w_patch, kx * v->Kp, S * v->P, D, kx * v->Kp, EpiPatchEmbed{v->x0, v->pos, D, v->P, T}, st, kx);
   const bool fuse = g_fuse_ln != 0;
-  const bool blk = !hilo && vit_fused(v, S);          // fused block kernels: LayerNorm inside the QKV / fc1 launches, attention behind the QKV GEMM
   launch_ln_fwd<false, true>(nv, v->x0, v->ln_pre_g, v->ln_pre_b, v->layers[0].x_in, M, T, v->cls, v->pos, v->x0, st, 1,
-                             (fuse && !blk) ? v->layers[0].ln1_g : nullptr, (fuse && !blk) ? v->layers[0].ln1_b : nullptr, (fuse && !blk) ? v->h : nullptr, hilo ? 1 : 0);
+                             fuse ? v->layers[0].ln1_g : nullptr, fuse ? v->layers[0].ln1_b : nullptr, fuse ? v->h : nullptr, hilo ? 1 : 0);
   for (int li = 0; li < v->L; ++li) {
     Layer& l = v->layers[li];
     float* x_next = li + 1 < v->L ? v->layers[li + 1].x_in : v->x_last;
-#ifdef APH_EXPERIMENTS
-    if (blk && vit_fused_attn(v, S)) {
-      vtimed(v, 2.0 * M * 3 * D * D + 4.0 * S * v->heads * T * T * 64, st, [&] { launch_qkv_attn(v, l, S, st); });
-    } else if (blk) {
-      vtimed(v, 2.0 * M * 3 * D * D, st, [&] { launch_ln_gemm(v, l.x_in, 1, M, l.ln1_g, l.ln1_b, l.w_qkv, 3 * D, EpiF16{l.qkv, 3 * D, l.b_qkv}, st); });
-      launch_attn_fwd(attn_args(v, l, S), st);
-    } else
-#endif
-    {
-      if (!(fuse && li == 0)) launch_ln_fwd<true, false>(nv, l.x_in, l.ln1_g, l.ln1_b, v->h, M, T, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, hilo ? 1 : 0);
-      if (hilo) {
-        // [r5] the lo half reaches the Q and K columns only; the V columns are summed over the hi half of the [hi | lo] rows alone (the first D of
-        // the 2 D columns of A and of [W | W]).  What the lo half repairs is the cancellation in h . W on weights whose residual stream carries
-        // large common offsets: through Q and K that error is amplified by the softmax, through V it enters the block linearly next to the f16
-        // rounding V is stored with anyway (CPU model, tools/precision_attribution.py: single-step gradient error 5.2e-4 through Q / K, 1.8e-4
-        // through V; on the GPU the single-step errors of the two forms are equal, profiles/r05_split_qk_only_ab.txt).  At full batch this is ONE
-        // launch of the wave-specialised kernel with two k-loop lengths (vit_gemm_ws.h).  Batches below that kernel's threshold are launch-bound,
-        // not MFMA-bound: they keep the plain launch over [hi | lo] on all 3 D columns (V a little more exact than it needs to be; a second
-        // launch per block would cost more than the shorter sums save: C1 726 -> 690 steps/s when it was tried).
-        const EpiF16 eq{l.qkv, 3 * D, l.b_qkv};
-        if (D % 128 == 0 && gemm_takes_ws(M, 2 * D, 3 * D, 2 * D)) {
-          vtimed(v, 2.0 * M * 3 * D * D, st, [&] { launch_gemm_ws(v->h, 2 * D, l.w_qkv2, 2 * D, M, 3 * D, 2 * D, eq, st, nullptr, D, D); });
-        } else {
-          vgemm(v, v->h, 2 * D, l.w_qkv2, 2 * D, M, 3 * D, 2 * D, eq, st, 2);      // (launch-bound sizes: one launch, the lo half on every column)
-        }
+    if (!(fuse && li == 0)) launch_ln_fwd<true, false>(nv, l.x_in, l.ln1_g, l.ln1_b, v->h, M, T, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, hilo ? 1 : 0);
+    if (hilo) {
+      // [r5] the lo half reaches the Q and K columns only; the V columns are summed over the hi half of the [hi | lo] rows alone (the first D of
+      // the 2 D columns of A and of [W | W]).  What the lo half repairs is the cancellation in h . W on weights whose residual stream carries
+      // large common offsets: through Q and K that error is amplified by the softmax, through V it enters the block linearly next to the f16
+      // rounding V is stored with anyway (CPU model, tools/precision_attribution.py: single-step gradient error 5.2e-4 through Q / K, 1.8e-4
+      // through V; on the GPU the single-step errors of the two forms are equal, profiles/r05_split_qk_only_ab.txt).  At full batch this is ONE
+      // launch of the wave-specialised kernel with two k-loop lengths (vit_gemm_ws.h).  Batches below that kernel's threshold are launch-bound,
+      // not MFMA-bound: they keep the plain launch over [hi | lo] on all 3 D columns (V a little more exact than it needs to be; a second
+      // launch per block would cost more than the shorter sums save: C1 726 -> 690 steps/s when it was tried).
+      const EpiF16 eq{l.qkv, 3 * D, l.b_qkv};
+      if (D % 128 == 0 && gemm_takes_ws(M, 2 * D, 3 * D, 2 * D)) {
+        vtimed(v, 2.0 * M * 3 * D * D, st, [&] { launch_gemm_ws(v->h, 2 * D, l.w_qkv2, 2 * D, M, 3 * D, 2 * D, eq, st, nullptr, D, D); });
       } else {
-        vgemm(v, v->h, D, l.w_qkv, D, M, 3 * D, D, EpiF16{l.qkv, 3 * D, l.b_qkv}, st);
+        vgemm(v, v->h, 2 * D, l.w_qkv2, 2 * D, M, 3 * D, 2 * D, eq, st, 2);      // (launch-bound sizes: one launch, the lo half on every column)
       }
-      launch_attn_fwd(attn_args(v, l, S), st);
+    } else {
+      vgemm(v, v->h, D, l.w_qkv, D, M, 3 * D, D, EpiF16{l.qkv, 3 * D, l.b_qkv}, st);
     }
+    launch_attn_fwd(attn_args(v, l, S), st);
     // Only the class token leaves the last block (VisionTransformer.forward: ln_post(x[:, 0, :])), so everything after
     // its attention runs on the S class rows alone: the same buffers addressed with a row pitch of T rows.
     const bool cls_only = li + 1 == v->L;
     const int Mr = cls_only ? S : M, rs = cls_only ? T : 1;
     vgemm(v, l.att, rs * D, l.w_o, D, Mr, D, D, EpiResidual{l.x_mid, l.x_in, rs * D, l.b_o}, st);
-#ifdef APH_EXPERIMENTS
-    if (blk) {
-      vtimed(v, 2.0 * Mr * 4 * D * D, st, [&] { launch_ln_gemm(v, l.x_mid, rs, Mr, l.ln2_g, l.ln2_b, l.w_fc1, 4 * D, EpiGelu{l.u, v->gact, 4 * D, l.b_fc1}, st); });
-    } else
-#endif
-    {
-      launch_ln_fwd<true, false>(nv, l.x_mid, l.ln2_g, l.ln2_b, v->h, Mr, T, nullptr, nullptr, nullptr, st, rs);
-      vgemm(v, v->h, D, l.w_fc1, D, Mr, 4 * D, D, EpiGelu{l.u, v->gact, 4 * D, l.b_fc1}, st);
-    }
+    launch_ln_fwd<true, false>(nv, l.x_mid, l.ln2_g, l.ln2_b, v->h, Mr, T, nullptr, nullptr, nullptr, st, rs);
+    vgemm(v, v->h, D, l.w_fc1, D, Mr, 4 * D, D, EpiGelu{l.u, v->gact, 4 * D, l.b_fc1}, st);
     vgemm(v, v->gact, 4 * D, l.w_fc2, 4 * D, Mr, D, 4 * D, EpiResidual{x_next, l.x_mid, rs * D, l.b_fc2}, st);
   }
   APH_ALLOW_SMEM(head_fwd_kernel, sizeof(float) * kHeadCuts * (D + 8 * 128));
@@ -715,45 +611,23 @@ static int vit_backward_impl(aph_vit* v, const float* d_genc, int S, void* d_pat
   // only the class rows carry gradient out of the head: the fp32 stream starts from zero; dx16 needs no clearing -- the
   // last block reads and writes its class rows only (row pitch T), and its ln_1 backward rewrites every row
   const bool fuse = g_fuse_ln != 0;      // (then the last block's ln_1 backward takes its residual from the class rows only: no fill)
-  const int s16 = (g_grad_stream_f16 != 0 && fuse && !vit_fused(v, S)) ? 1 : 0;      // f16-only gradient stream (measurement switch; needs the fused LayerNorm pairs' row conventions)
+  const int s16 = (g_grad_stream_f16 != 0 && fuse) ? 1 : 0;      // f16-only gradient stream (measurement switch; needs the fused LayerNorm pairs' row conventions)
   if (!fuse) zero_fill_async(v->dx, sizeof(float) * (size_t)M * D, st);            // (a kernel node, not a memset node: see zero_fill_async)
   APH_LAUNCH(head_bwd_kernel, dim3(S), dim3(D), sizeof(float) * v->E, st, d_genc, (const float*)v->x_last,
              (const float*)v->ln_post_g, (const float*)v->projT, v->dx, v->dx16, T, D, v->E);
-  // fused backward (vit_block.h, -DAPH_EXPERIMENTS builds): a block's closing ln_1 backward is not launched; it runs as the prologue of the NEXT (lower) block's fc2
-  // dgrad -- `pending` carries it over: dy = v->dh, LayerNorm input = the upper block's x_in, residual = v->dx (only the rows % res_T == 0)
-  const bool blk = vit_fused(v, S);
-  bool pending = false;
-  int pending_res_T = 0;
   for (int li = v->L - 1; li >= 0; --li) {
     Layer& l = v->layers[li];
     const bool cls_only = li + 1 == v->L;          // see aph_vit_forward: the last block's MLP / out-proj saw class rows only
     const int Mr = cls_only ? S : M, rs = cls_only ? T : 1;
     if (cls_only) zero_fill_async(v->datt, sizeof(half_t) * (size_t)M * D, st);   // no gradient into the other rows' attention output
-    const float* res2 = v->dx;                      // residual of this block's ln_2 backward
-#ifdef APH_EXPERIMENTS
-    if (pending) {
-      const Layer& up = v->layers[li + 1];
-      vtimed(v, 2.0 * M * 4 * D * D, st, [&] {
-        launch_lnbwd_gemm(v, v->dh, up.x_in, up.ln1_g, v->dx, v->dx2, pending_res_T, M, l.w_fc2T, 4 * D, EpiGeluBwd{v->du, l.u, 4 * D}, st);
-      });
-      res2 = v->dx2;
-      pending = false;
-    } else
-#endif
-    {
-      vgemm(v, v->dx16, rs * D, l.w_fc2T, D, Mr, 4 * D, D, EpiGeluBwd{v->du, l.u, 4 * D}, st);
-    }
+    vgemm(v, v->dx16, rs * D, l.w_fc2T, D, Mr, 4 * D, D, EpiGeluBwd{v->du, l.u, 4 * D}, st);
     vgemm(v, v->du, 4 * D, l.w_fc1T, 4 * D, Mr, D, 4 * D, EpiF16{v->dh, D, nullptr}, st);
     if (s16) launch_ln_bwd<true, false>(nv, v->dh, l.x_mid, l.ln2_g, v->dx16, nullptr, v->dx16, Mr, T, st, rs, 0, nullptr, nullptr, 1);
-    else launch_ln_bwd<true, false>(nv, v->dh, l.x_mid, l.ln2_g, res2, v->dx, v->dx16, Mr, T, st, rs);
+    else launch_ln_bwd<true, false>(nv, v->dh, l.x_mid, l.ln2_g, v->dx, v->dx, v->dx16, Mr, T, st, rs);
     vgemm(v, v->dx16, rs * D, l.w_oT, D, Mr, D, D, EpiF16{v->datt, rs * D, nullptr}, st);
     launch_attn_bwd(attn_args(v, l, S), st);
     vgemm(v, v->dqkv, 3 * D, l.w_qkvT, 3 * D, M, D, 3 * D, EpiF16{v->dh, D, nullptr}, st);
-    if (blk && li > 0) {      // deferred into block li - 1's first launch
-      pending = true;
-      pending_res_T = (fuse && cls_only) ? T : 0;
-    }
-    else if (fuse && li == 0)      // ln_1 backward and ln_pre backward as one kernel: writes the patch rows of dx0_16 only
+    if (fuse && li == 0)      // ln_1 backward and ln_pre backward as one kernel: writes the patch rows of dx0_16 only
       launch_ln_bwd<true, false>(nv, v->dh, l.x_in, l.ln1_g, s16 ? (const void*)v->dx16 : (const void*)v->dx, nullptr, v->dx0_16, M, T, st, 1, cls_only ? T : 0, v->x0, v->ln_pre_g, s16);
     else if (s16)
       launch_ln_bwd<true, false>(nv, v->dh, l.x_in, l.ln1_g, v->dx16, nullptr, v->dx16, M, T, st, 1, cls_only ? T : 0, nullptr, nullptr, 1);
@@ -892,30 +766,6 @@ int aph_vit_set_grad_stream_f16(int on) {
   return prev;
 }
 
-#ifdef APH_EXPERIMENTS
-// measurement variants of the T <= 56 attention backward (WRONG results): 0 = the kernel, 1 = no products (zeros stored), 2 = no stores, 3 = loads + staging only
-int aph_attn_set_ablate(int mode) {
-  const int prev = g_attn_ablate;
-  g_attn_ablate = mode < 0 || mode > 3 ? 0 : mode;
-  return prev;
-}
-// largest batch (token rows S * T) that runs the fused block kernels of vit_block.h (0 = never).  Returns the previous value.
-int aph_vit_set_fused_max_rows(int rows) {
-  const int prev = g_fused_max_rows;
-  g_fused_max_rows = rows < 0 ? 0 : rows;
-  return prev;
-}
-
-// the (cut, head) LayerNorm + QKV + attention kernel inside the fused forward: 0 = never, 1 = while S x heads workgroups fit the chip in one
-// round (default), 2 = always.  Returns the previous value.
-int aph_vit_set_fused_attn(int mode) {
-  const int prev = g_fused_attn;
-  g_fused_attn = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
-  return prev;
-}
-
-#endif  // APH_EXPERIMENTS
-
 int aph_gemm_set_mfma32(int on) {
   const int prev = gemm_mfma32();
   gemm_mfma32() = on ? 1 : 0;
@@ -929,16 +779,8 @@ int aph_gemm_set_ws_min_tiles(int tiles) {
   return prev;
 }
 
-// small-M GEMMs (below the wave-specialised kernel's threshold) on the register-staged kernels of vit_gemm_rs.h (1, default) or on the shared-ring
+// small-M GEMMs (below the wave-specialised kernel's threshold) on the register-staged split-K kernel of vit_gemm_rs.h (1, default) or on the shared-ring
 // tile configurations of vit_gemm.h (0).  Returns the previous value.
-#ifdef APH_EXPERIMENTS
-// blocked attention backward (64 < tokens <= 256): 1 = one kernel (default), 0 = the dQ + dK/dV pair.  Returns the previous value.
-int aph_attn_set_bwd_one(int on) {
-  const int prev = g_attn_bwd_one;
-  g_attn_bwd_one = on ? 1 : 0;
-  return prev;
-}
-#endif
 int aph_gemm_set_rs(int mode) {
   const int prev = gemm_rs_mode();
   gemm_rs_mode() = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
@@ -994,7 +836,7 @@ int aph_mfma_rate(int blocks, int iters, const void* d_src, float* d_out, void* 
 int aph_gemm_ws_probe(const void* d_A, const void* d_Bt, int M, int N, int K, void* d_out, void* d_out2, const float* d_bias, int epi_kind,
                       unsigned long long* d_trace, void* stream_) {
   APH_TRY
-  if (!d_A || !d_Bt || !d_out || M < 1 || N % 128 || K % GEMM_BK || N > 4096 || !gemm8_addressable(M, K, N, K))
+  if (!d_A || !d_Bt || !d_out || M < 1 || N % 128 || K % GEMM_BK || N > 4096 || !gemm_addressable32(M, K, N, K))
     return aph_fail(APH_ERR_ARG, "aph_gemm_ws_probe: bad shape");
   const half_t* A = (const half_t*)d_A;
   const half_t* B = (const half_t*)d_Bt;
@@ -1008,61 +850,28 @@ int aph_gemm_ws_probe(const void* d_A, const void* d_Bt, int M, int N, int K, vo
   APH_CATCH
 }
 
-// Measurement hook: the register-staged small-M kernels with an f16 output and per-phase stamps of the chip-wide 100 MHz clock.
-// kind 0 = split-K 64x64 (stamps: entry, first fragments read, main loop done, past the barrier, end), 1 = A-resident 64x256 (entry, fill
-// issued, fill barrier passed, main loop done, end).  d_trace: (workgroups x 8) uint64 or NULL.
+// Measurement hook: the register-staged split-K 64x64 kernel with an f16 output and per-phase stamps of the chip-wide 100 MHz clock (entry,
+// first fragments read, main loop done, past the barrier, end).  kind: 0 only.  d_trace: (workgroups x 8) uint64 or NULL.
 int aph_gemm_rs_probe(const void* d_A, const void* d_Bt, int M, int N, int K, void* d_out, int kind, unsigned long long* d_trace, void* stream_) {
   APH_TRY
-#ifdef APH_EXPERIMENTS
-  const bool fits = kind == 0 ? gemm_sk_fits(N, K) : gemm_ar_fits(N, K);
-#else
-  const bool fits = gemm_sk_fits(N, K);
-#endif
-  if (!d_A || !d_Bt || !d_out || M < 1 || !gemm8_addressable(M, K, N, K) || !fits) return aph_fail(APH_ERR_ARG, "aph_gemm_rs_probe: bad shape");
+  if (kind != 0) return aph_fail(APH_ERR_ARG, "aph_gemm_rs_probe: kind %d is not a kernel of this library (0 = split-K register-staged)", kind);
+  if (!d_A || !d_Bt || !d_out || M < 1 || !gemm_addressable32(M, K, N, K) || !gemm_sk_fits(N, K)) return aph_fail(APH_ERR_ARG, "aph_gemm_rs_probe: bad shape");
   const EpiF16 epi{(half_t*)d_out, N, nullptr};
-#ifndef APH_EXPERIMENTS
-  if (kind != 0) return aph_fail(APH_ERR_UNSUPPORTED, "aph_gemm_rs_probe: kinds 1 / 2 (A-resident kernels) exist in -DAPH_EXPERIMENTS builds only");
   launch_gemm_sk<4>((const half_t*)d_A, K, (const half_t*)d_Bt, K, M, N, K, epi, (hipStream_t)stream_, d_trace);
   return aph_check_launch("aph_gemm_rs_probe");
-#else
-  if (kind == 2) {        // d_Bt = the fragment-major image written by aph_gemm_pack_frag (experiment: K = 768 only)
-    if (K != 768) return aph_fail(APH_ERR_ARG, "aph_gemm_rs_probe: kind 2 is instantiated for K = 768");
-    using C = GemmAR<4>;
-    APH_ALLOW_SMEM((gemm_arp_kernel<4, 24, 8, EpiF16>), C::smem(768));
-    APH_LAUNCH((gemm_arp_kernel<4, 24, 8, EpiF16>), dim3((N / C::BN) * ((M + C::BM - 1) / C::BM)), dim3(256), C::smem(768), (hipStream_t)stream_,
-               (const half_t*)d_A, K, (const half_t*)d_Bt, M, N, epi, d_trace);
-    return aph_check_launch("aph_gemm_rs_probe");
-  }
-  if (kind == 0) launch_gemm_sk<4>((const half_t*)d_A, K, (const half_t*)d_Bt, K, M, N, K, epi, (hipStream_t)stream_, d_trace);
-  else launch_gemm_ar<4, 8>((const half_t*)d_A, K, (const half_t*)d_Bt, K, M, N, K, epi, (hipStream_t)stream_, d_trace);
-  return aph_check_launch("aph_gemm_rs_probe");
-#endif
   APH_CATCH
 }
-
-#ifdef APH_EXPERIMENTS
-// Bt [N, K] f16 -> fragment-major image for the A-resident kernel's 256-column groups (experiment hook)
-int aph_gemm_pack_frag(const void* d_Bt, int N, int K, void* d_out, void* stream_) {
-  APH_TRY
-  if (!d_Bt || !d_out || N % 256 || K % 32) return aph_fail(APH_ERR_ARG, "aph_gemm_pack_frag: bad shape");
-  const size_t total = (size_t)(N / 16) * (K / 32) * 64;
-  APH_LAUNCH((pack_frag_kernel<4>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, (const half_t*)d_Bt, (half_t*)d_out, N, K);
-  return aph_check_launch("aph_gemm_pack_frag");
-  APH_CATCH
-}
-
-#endif
 
 // the attention kernels alone (unit tests, micro-benchmarks): mode 0 = forward (qkv -> att, lse), 1 = backward
 // ((qkv, att, lse, datt) -> dqkv).  qkv / dqkv [S*T, 3*heads*64] f16, att / datt [S*T, heads*64] f16, lse [S*heads*T] f32,
-// d_delta: S*heads*T floats of scratch, needed by the backward when T > 64.
-int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* d_delta, void* d_dqkv, int S, int T, int heads,
+// d_delta: unused (no kernel takes row-dot scratch); the argument stays so that the prototype does not change.
+int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* /*d_delta*/, void* d_dqkv, int S, int T, int heads,
                   int mode, void* stream_) {
   APH_TRY
   if (!d_qkv || !d_att || !d_lse || S < 1 || T < 1 || T > 256 || heads < 1 || (mode != 0 && mode != 1) ||
-      (mode == 1 && (!d_datt || !d_dqkv || (T > AT_T && !d_delta))))
+      (mode == 1 && (!d_datt || !d_dqkv)))
     return aph_fail(APH_ERR_ARG, "aph_attn_test: bad argument");
-  const AttnArgs a{(const half_t*)d_qkv, (half_t*)d_att, d_lse, (const half_t*)d_datt, d_delta, (half_t*)d_dqkv, S, T, heads};
+  const AttnArgs a{(const half_t*)d_qkv, (half_t*)d_att, d_lse, (const half_t*)d_datt, (half_t*)d_dqkv, S, T, heads};
   if (mode == 0) launch_attn_fwd(a, (hipStream_t)stream_);
   else launch_attn_bwd(a, (hipStream_t)stream_);
   return aph_check_launch("aph_attn_test");
@@ -1101,22 +910,17 @@ int aph_gemm_f16(const void* d_A, const void* d_Bt, int M, int N, int K, float* 
 }
 
 // same with explicit leading dimensions (row pitches in elements) and tile configuration
-// (0 = automatic, 1 = 64x64, 2 = 256x128, 4 = 256x256 phased [needs N % 256 == 0], 5 = 256x128 wave-specialised persistent, 8 / 9 = 64x64 split-K x2 / x4,
+// (0 = automatic, 1 = 64x64, 2 = 256x128, 5 = 256x128 wave-specialised persistent, 8 / 9 = 64x64 split-K x2 / x4,
 // 10 = 128x128 4-stage, 11 = 128x128 4 waves 2-stage (two workgroups per CU), 12 = 256x128 on 4 waves,
-// 14 / 15 = 64x64 register-staged split-K (4 / 3 k-steps in flight per wave), 16 / 17 = 64x256 A-resident (8 / 4 k-steps in flight; N % 256 == 0, K <= 1024),
-// 22 / 24 = 128x128 split-K x2 / x4) -- unit tests and tuning sweeps
-#ifdef APH_EXPERIMENTS
-static bool gemm_ar_addressable(int N, int K) { return gemm_ar_fits(N, K); }
-#else
-static bool gemm_ar_addressable(int, int) { return true; }      // (tile_cfg 16 / 17 are refused further down in product builds)
-#endif
+// 14 / 15 = 64x64 register-staged split-K (4 / 3 k-steps in flight per wave), 22 / 24 = 128x128 split-K x2 / x4) -- unit tests and tuning sweeps;
+// any other tile_cfg is refused
 int aph_gemm_f16_ld(const void* d_A, int lda, const void* d_Bt, int ldb, int M, int N, int K, float* d_C, int tile_cfg, void* stream_) {
   APH_TRY
   const bool nostore = (tile_cfg & 0x100) != 0;
   tile_cfg &= 0xff;
+  if (!(tile_cfg == 0 || tile_cfg == 1 || tile_cfg == 2 || tile_cfg == 5 || (tile_cfg >= 8 && tile_cfg <= 12) || tile_cfg == 14 || tile_cfg == 15 || tile_cfg == 22 || tile_cfg == 24))
+    return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: tile_cfg %d is not a configuration of this library (0, 1, 2, 5, 8 ... 12, 14, 15, 22, 24)", tile_cfg);
   if (!d_A || !d_Bt || !d_C || M < 1 || N % 128 || K % GEMM_BK || N < 1 || K < 1 || lda < K || ldb < K || (lda & 7) || (ldb & 7) ||
-      !(tile_cfg == 0 || tile_cfg == 1 || tile_cfg == 2 || tile_cfg == 4 || tile_cfg == 5 || (tile_cfg >= 8 && tile_cfg <= 12) || (tile_cfg >= 14 && tile_cfg <= 17) || tile_cfg == 22 || tile_cfg == 24) ||
-      (tile_cfg >= 16 && tile_cfg <= 17 && (!gemm8_addressable(M, lda, N, ldb) || !gemm_ar_addressable(N, K))) || (tile_cfg == 4 && (N % 256 || !gemm8_addressable(M, lda, N, ldb))) ||
       !gemm_test_cfg_fits(tile_cfg, M, lda, N, ldb, K))
     return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: bad shape");
   const half_t* A = (const half_t*)d_A;
@@ -1126,32 +930,18 @@ int aph_gemm_f16_ld(const void* d_A, int lda, const void* d_Bt, int ldb, int M, 
   if (nostore) {          // measurement only: the same main loops with the output stores compiled out of the taken path
     const EpiNoStore en{d_C, N};
     if (tile_cfg == 2) launch_gemm_cfg<GemmBig>(A, lda, B, ldb, M, N, K, en, st);
-#ifdef APH_EXPERIMENTS
-    else if (tile_cfg == 4) launch_gemm8(A, lda, B, ldb, M, N, K, en, st);
-#endif
     else if (tile_cfg == 5) launch_gemm_ws_cfg<GemmWS>(A, lda, B, ldb, M, N, K, en, st, nullptr);
-    else return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: the no-store variant exists for tile_cfg 2 and 5 (4: -DAPH_EXPERIMENTS builds)");
+    else return aph_fail(APH_ERR_ARG, "aph_gemm_f16_ld: the no-store variant exists for tile_cfg 2 and 5");
     return aph_check_launch("aph_gemm_f16_ld");
   }
   // the measurement-only families; everything else goes through gemm_f16_launch_cfg
-#ifdef APH_EXPERIMENTS
-  if (tile_cfg == 4) launch_gemm8(A, lda, B, ldb, M, N, K, epi, st);
-#else
-  if (tile_cfg == 4) return aph_fail(APH_ERR_UNSUPPORTED, "aph_gemm_f16_ld: tile_cfg 4 (phased 256x256 kernel) exists in -DAPH_EXPERIMENTS builds only");
-#endif
-  else if (tile_cfg == 22 || tile_cfg == 24) {                // split-K (2 / 4 ways) of the 128x128 configuration, private workspace
+  if (tile_cfg == 22 || tile_cfg == 24) {                // split-K (2 / 4 ways) of the 128x128 configuration, private workspace
     SplitKSpace* ws = nullptr;
     if (const int rc = gemm_test_splitk_space(&ws)) return rc;
     launch_gemm_splitk<GemmMidDeep8>(A, lda, B, ldb, M, N, K, epi, tile_cfg == 22 ? 2 : 4, *ws, st);
   }
   else if (tile_cfg == 11) launch_gemm_cfg<GemmPair>(A, lda, B, ldb, M, N, K, epi, st);
   else if (tile_cfg == 12) launch_gemm_cfg<GemmFat>(A, lda, B, ldb, M, N, K, epi, st);
-#ifdef APH_EXPERIMENTS
-  else if (tile_cfg == 16) launch_gemm_ar<4, 8>(A, lda, B, ldb, M, N, K, epi, st);
-  else if (tile_cfg == 17) launch_gemm_ar<4, 4>(A, lda, B, ldb, M, N, K, epi, st);
-#else
-  else if (tile_cfg == 16 || tile_cfg == 17) return aph_fail(APH_ERR_UNSUPPORTED, "aph_gemm_f16_ld: tile_cfg 16 / 17 (A-resident kernel) exist in -DAPH_EXPERIMENTS builds only");
-#endif
   else if (const int rc = gemm_f16_launch_cfg(A, lda, B, ldb, M, N, K, epi, tile_cfg, nullptr, st)) return rc;
   return aph_check_launch("aph_gemm_f16_ld");
   APH_CATCH

@@ -223,9 +223,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const half_t* __rest
 // at 170 VGPRs under a 168-register bound the compiler spilled one address pair, and its reload -- `scratch_load` + `s_waitcnt vmcnt(0)`,
 // vmcnt being one in-order counter -- sat right behind the prefetch loads of the next item: every wave waited for its prefetch to LAND
 // before starting the products the prefetch was meant to hide behind (found in the ISA; round 2's 35.7 -> 30.7 us was what survived).
-// ABL (measurement only, -DAPH_EXPERIMENTS builds, tools/exp/attn_ablate.py -- WRONG results): 1 = no products (the stores write zeros: loads +
-// staging + stores, the memory skeleton), 2 = no stores (loads + staging + products), 3 = loads + staging only
-template <int RB, int ABL = 0>            // rows kept per row-major LDS tile: 56 (T <= 56: 3 workgroups per CU) or 64
+template <int RB>            // rows kept per row-major LDS tile: 56 (T <= 56: 3 workgroups per CU) or 64
 __global__ __launch_bounds__(256, RB == 56 ? 3 : 2) void attn_bwd_mfma_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ datt,
                                                            const float* __restrict__ lse, half_t* __restrict__ dqkv, int T, int heads, int items) {
   constexpr int RT = RB * 64;                    // halfs per row-major tile
@@ -264,20 +262,6 @@ __global__ __launch_bounds__(256, RB == 56 ? 3 : 2) void attn_bwd_mfma_kernel(co
     const int next = item + gridDim.x;
     if (next < items) fetch(next);               // in flight during the products and stores below
     half_t* dbase = dqkv + (size_t)s * T * ld + h * 64;
-    if (ABL & 1) {          // ablation: the three output tiles as zeros (same store pattern), or nothing at all
-      if (active && !(ABL & 2)) {
-        const int i = w * 16 + c16;
-#pragma unroll
-        for (int part = 0; part < 3; ++part)
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt)
-            if (i < T) store_h4(dbase + (size_t)i * ld + part * D + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
-      }
-      if (next >= items) break;
-      item = next;
-      __syncthreads();
-      continue;
-    }
     if (active) {
       // ---- phase A: wave = query tile.  S^T = K Q^T, dP^T = V dO^T (lane: query i, keys jt*16 + g*4 + r)
       const int it = w, i = it * 16 + c16;
@@ -322,8 +306,7 @@ __global__ __launch_bounds__(256, RB == 56 ? 3 : 2) void attn_bwd_mfma_kernel(co
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int q = it * 16 + g * 4 + r;
-        if (!(ABL & 2) && q < T) store_h4(dbase + (size_t)q * ld + 4 * c16, o[0][r], o[1][r], o[2][r], o[3][r]);
-        if ((ABL & 2) && o[0][r] == 1.2345e33f) store_h4(dbase, o[0][r], o[1][r], o[2][r], o[3][r]);        // (keeps the products alive)
+        if (q < T) store_h4(dbase + (size_t)q * ld + 4 * c16, o[0][r], o[1][r], o[2][r], o[3][r]);
       }
     } else if (lane < 16) {
       Ds[w * 16 + lane] = 0.f;                     // query tiles past T (their dO rows are zero)
@@ -374,11 +357,10 @@ __global__ __launch_bounds__(256, RB == 56 ? 3 : 2) void attn_bwd_mfma_kernel(co
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int kj = jt * 16 + g * 4 + r;
-        if (!(ABL & 2) && kj < T) {
+        if (kj < T) {
           store_h4(dbase + (size_t)kj * ld + D + 4 * c16, ok[0][r], ok[1][r], ok[2][r], ok[3][r]);
           store_h4(dbase + (size_t)kj * ld + 2 * D + 4 * c16, ov[0][r], ov[1][r], ov[2][r], ov[3][r]);
         }
-        if ((ABL & 2) && ok[0][r] + ov[0][r] == 1.2345e33f) store_h4(dbase, ok[0][r], ok[1][r], ov[2][r], ov[3][r]);
       }
     }
     if (next >= items) break;
@@ -392,11 +374,10 @@ __global__ __launch_bounds__(256, RB == 56 ? 3 : 2) void attn_bwd_mfma_kernel(co
 // Row-major operand images are [NB*64][64] (at_off on the global row), transposed slot-permuted images are NB tiles
 // of [64 d][64 slots]; probabilities / dS of a 32-token block are one B fragment, so the second product streams over
 // 32-token blocks.  The forward keeps a query tile's whole score row in registers (<= 16 tiles) -- exact softmax, no
-// online rescaling.  The backward is two kernels so that each fits LDS: dQ with K, V, K^T resident (query tiles
-// stationary per wave, Q / dO fragments straight from global) and dK/dV with Q, dO, Q^T, dO^T resident (key tiles
-// stationary); both recompute P = exp(S/8 - lse) per 32-block from the saved log-sum-exp.
+// online rescaling.  The backward is one kernel (attn_bwd_one_g_kernel below), key tiles stationary; it recomputes
+// P = exp(S/8 - lse) per 32-block from the saved log-sum-exp.
 // ---------------------------------------------------------------------------------------------------------------
-// (Round 4, measured and rejected: these three kernels as PERSISTENT workgroups with the next item's operand rows and the next tile round's
+// (Round 4, measured and rejected: the forward and the then two backward kernels as PERSISTENT workgroups with the next item's operand rows and the next tile round's
 // fragments prefetched into registers, like the one-tile backward above -- forward 70.0 us against 65.6, backward 137.9 against 143.9 at C4's
 // shape (profiles/r04_attn_bench.txt).  Nothing to hide: at T = 197 a lane holds 52 scores of its query and the softmax arithmetic on them --
 // scale, mask, max, subtract, exp, sum, convert: ~15 VALU slots per score, 2.6 k clocks per query tile next to 0.9 k of MFMA -- is what a
@@ -487,161 +468,10 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_g_kernel(const half_t* __re
   }
 }
 
-#ifdef APH_EXPERIMENTS       // the round-3 / round-4 backward as two kernels, each recomputing P and dS: superseded by attn_bwd_one_g_kernel below
-                             // (131-139 -> 113-115 us at C4's shape, profiles/r05_attn_bwd_one.txt); kept compilable for A/B runs only
-// dQ (query tiles stationary) + the row dots delta_i = dO_i . O_i, written for the dK/dV kernel
-template <int NB>
-__global__ __launch_bounds__(512) void attn_bwd_dq_g_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ att,
-                                                           const half_t* __restrict__ datt, const float* __restrict__ lse,
-                                                           float* __restrict__ delta, half_t* __restrict__ dqkv, int T, int heads) {
-  APH_DYN_SMEM(smem);
-  half_t* Ks = reinterpret_cast<half_t*>(smem);
-  half_t* Vs = Ks + NB * 4096;
-  half_t* Kt = Vs + NB * 4096;
-  const int s = blockIdx.x / heads, h = blockIdx.x - s * heads;
-  const int D = heads * 64, ld = 3 * D;
-  const half_t* base = qkv + (size_t)s * T * ld + h * 64;
-  const half_t* dob = datt + (size_t)s * T * D + h * 64;
-  const half_t* ob = att + (size_t)s * T * D + h * 64;
-  for (int idx = threadIdx.x; idx < 2 * NB * 64; idx += 512) {
-    if (idx < NB * 64) atg_stage<NB>(base + D, ld, T, Ks, Kt, idx, false);      // (natural row order below: at_off)
-    else atg_stage<NB>(base + 2 * D, ld, T, Vs, nullptr, idx - NB * 64);
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c16 = lane & 15, g = lane >> 4;
-  half_t* dbase = dqkv + (size_t)s * T * ld + h * 64;
-  for (int it = wave; it * 16 < T; it += 8) {
-    const int i = it * 16 + c16;
-    const bool live = i < T;
-    half8 qf[2], of[2];
-    float Di = 0.f;
-#pragma unroll
-    for (int kd = 0; kd < 2; ++kd) {
-      qf[kd] = ld_frag_global(base + (size_t)i * ld + kd * 32 + g * 8, live);
-      of[kd] = ld_frag_global(dob + (size_t)i * D + kd * 32 + g * 8, live);
-      const half8 ov = ld_frag_global(ob + (size_t)i * D + kd * 32 + g * 8, live);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) Di += (float)ov[e] * (float)of[kd][e];
-    }
-    Di += __shfl_xor(Di, 16);
-    Di += __shfl_xor(Di, 32);
-    const float Li2 = live ? lse[((size_t)s * heads + h) * T + i] * kLog2e : 0.f;
-    if (live && g == 0) delta[((size_t)s * heads + h) * T + i] = Di;
-    f32x4 o[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2 * NB; ++kb) {
-      if (kb * 32 < T) {
-        f32x4 st[2], dp[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          st[u] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          const int jr = (2 * kb + u) * 16 + c16;
-#pragma unroll
-          for (int kd = 0; kd < 2; ++kd) {
-            st[u] = mfma_16x16x32_f16(at_frag(Ks, jr, kd * 4 + g), qf[kd], st[u]);
-            dp[u] = mfma_16x16x32_f16(at_frag(Vs, jr, kd * 4 + g), of[kd], dp[u]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) st[u][r] = at_ds(at_p(st[u][r], Li2), dp[u][r], Di);      // dS^T
-        }
-        const half8 df = pack8(st[0], st[1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] = mfma_16x16x32_f16(at_frag(Kt + (kb >> 1) * 4096, dt * 16 + c16, (kb & 1) * 4 + g), df, o[dt]);
-      }
-    }
-    if (live) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_h4(dbase + (size_t)i * ld + dt * 16 + g * 4, o[dt][0], o[dt][1], o[dt][2], o[dt][3]);
-    }
-  }
-}
-
-// dK, dV (key tiles stationary)
-template <int NB>
-__global__ __launch_bounds__(512) void attn_bwd_dkv_g_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ datt,
-                                                            const float* __restrict__ lse, const float* __restrict__ delta,
-                                                            half_t* __restrict__ dqkv, int T, int heads) {
-  APH_DYN_SMEM(smem);
-  half_t* Qs = reinterpret_cast<half_t*>(smem);
-  half_t* Os = Qs + NB * 4096;
-  half_t* Qt = Os + NB * 4096;
-  half_t* Ot = Qt + NB * 4096;
-  float* Ls = reinterpret_cast<float*>(Ot + NB * 4096);
-  float* Ds = Ls + NB * 64;
-  const int s = blockIdx.x / heads, h = blockIdx.x - s * heads;
-  const int D = heads * 64, ld = 3 * D;
-  const half_t* base = qkv + (size_t)s * T * ld + h * 64;
-  const half_t* dob = datt + (size_t)s * T * D + h * 64;
-  for (int idx = threadIdx.x; idx < 2 * NB * 64; idx += 512) {
-    if (idx < NB * 64) atg_stage<NB>(base, ld, T, Qs, Qt, idx, false);      // (natural row order below: at_off)
-    else atg_stage<NB>(dob, D, T, Os, Ot, idx - NB * 64, false);
-  }
-  for (int r = threadIdx.x; r < NB * 64; r += 512) {
-    Ls[r] = r < T ? lse[((size_t)s * heads + h) * T + r] * kLog2e : 0.f;
-    Ds[r] = r < T ? delta[((size_t)s * heads + h) * T + r] : 0.f;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c16 = lane & 15, g = lane >> 4;
-  half_t* dbase = dqkv + (size_t)s * T * ld + h * 64;
-  for (int jt = wave; jt * 16 < T; jt += 8) {
-    const int j = jt * 16 + c16;
-    const bool live = j < T;
-    half8 kf[2], vf[2];
-#pragma unroll
-    for (int kd = 0; kd < 2; ++kd) {
-      kf[kd] = ld_frag_global(base + (size_t)j * ld + D + kd * 32 + g * 8, live);
-      vf[kd] = ld_frag_global(base + (size_t)j * ld + 2 * D + kd * 32 + g * 8, live);
-    }
-    f32x4 ok[4], ov[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { ok[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; ov[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-    for (int qb = 0; qb < 2 * NB; ++qb) {
-      if (qb * 32 < T) {
-        f32x4 sq[2], dq[2], pp[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          sq[u] = f32x4{0.f, 0.f, 0.f, 0.f}; dq[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          const int t16 = (2 * qb + u) * 16;
-#pragma unroll
-          for (int kd = 0; kd < 2; ++kd) {
-            sq[u] = mfma_16x16x32_f16(at_frag(Qs, t16 + c16, kd * 4 + g), kf[kd], sq[u]);
-            dq[u] = mfma_16x16x32_f16(at_frag(Os, t16 + c16, kd * 4 + g), vf[kd], dq[u]);
-          }
-          const f32x4 L4 = *reinterpret_cast<const f32x4*>(Ls + t16 + g * 4);
-          const f32x4 D4 = *reinterpret_cast<const f32x4*>(Ds + t16 + g * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float p = at_p(sq[u][r], L4[r]);       // L4 = lse * log2 e
-            pp[u][r] = p;
-            sq[u][r] = at_ds(p, dq[u][r], D4[r]);     // dS
-          }
-        }
-        const half8 pf = pack8(pp[0], pp[1]), sf = pack8(sq[0], sq[1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          ov[dt] = mfma_16x16x32_f16(at_frag(Ot + (qb >> 1) * 4096, dt * 16 + c16, (qb & 1) * 4 + g), pf, ov[dt]);
-          ok[dt] = mfma_16x16x32_f16(at_frag(Qt + (qb >> 1) * 4096, dt * 16 + c16, (qb & 1) * 4 + g), sf, ok[dt]);
-        }
-      }
-    }
-    if (live) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        store_h4(dbase + (size_t)j * ld + D + dt * 16 + g * 4, ok[dt][0], ok[dt][1], ok[dt][2], ok[dt][3]);
-        store_h4(dbase + (size_t)j * ld + 2 * D + dt * 16 + g * 4, ov[dt][0], ov[dt][1], ov[dt][2], ov[dt][3]);
-      }
-    }
-  }
-}
-
-#endif  // APH_EXPERIMENTS
-
 // ---------------------------------------------------------------------------------------------------------------
 // [r5] The blocked backward as ONE kernel: P = exp(S / 8 - lse) and dS are formed ONCE per (query, key).
-// The two kernels above each recompute them because the two contractions want them in transposed register layouts: dK / dV contract over
+// The dQ + dK/dV kernel pair this replaced (131-139 -> 113-115 us at C4's shape, profiles/r05_attn_bwd_one.txt) recomputed them in each kernel
+// because the two contractions want them in transposed register layouts: dK / dV contract over
 // QUERIES (the probabilities must be a B fragment with lane = key), dQ contracts over KEYS (lane = query) -- and at T = 197 the softmax
 // arithmetic on a lane's scores, not the matrix pipe, is what these kernels spend their time on (note above).  Here the key-stationary form
 // is kept (wave w owns the key tiles w, w + 8: K / V fragments and the dK / dV accumulators stay in registers for the whole kernel) and dS

@@ -4,10 +4,8 @@
 //
 // Both operands are K-contiguous, so the forward (activations x weight^T) and the dgrad (d_out x weight, using a
 // pre-transposed weight copy) run through the same kernels.  Tile configurations (launch_gemm picks one per shape):
-//   * 256x256x64 "phased" kernel (gemm8_f16_kernel): 8 waves (2x4 of 128x64), 2 x 64 KiB stages, four phases per k-tile,
-//     the two wave groups one barrier apart -- shapes with >= 400 such tiles: fc1 / fc2^T / patch-embed dgrad (N = 3072) at full
-//     batch (456 tiles).  QKV (N = 2304: 342 tiles = 1.34 rounds of 256 CUs) is NOT among them;
-//   * 256x128x64, 8 waves (4x2 of 64x64), 3-stage ring, 144 KiB LDS -- QKV and every N = 768 GEMM at full batch;
+//   * 256x128x64 wave-specialised persistent kernel (vit_gemm_ws.h) -- shapes with >= 160 such tiles: the GEMMs of a full batch;
+//   * 256x128x64, 8 waves (4x2 of 64x64), 3-stage ring, 144 KiB LDS -- the same shapes when the wave-specialised kernel is switched off;
 //   * 128x128x64, 8 waves (4x2 of 32x64), 4-stage ring, 128 KiB LDS -- half-batch shards, wide outputs of small shards;
 //   *  64x 64x64, 4 waves (2x2 of 32x32), 4-stage ring,  64 KiB LDS (2 workgroups per CU) -- small M; two-pass split-K
 //     when only a handful of tiles exist (the class-row GEMMs of the last block).
@@ -21,7 +19,7 @@
 //   * operands are swapped at the MFMA (weights as the A fragment) and the accumulators leave through LDS, so every
 //     lane stores 8 consecutive columns of one row: whole 128-byte lines, 16/32-byte accesses;
 //   * XCD-aware tile order (T1): the column tiles that re-read one A panel run on the same XCD / L2.
-// Constraints: N % 128 == 0 (N % 256 for the phased kernel), K % 64 == 0 (true for every ViT-B linear); M is arbitrary
+// Constraints: N % 128 == 0, K % 64 == 0 (true for every ViT-B linear); M is arbitrary
 // (loads clamp the row, stores are predicated).
 #pragma once
 #include "aph_device.h"
@@ -304,267 +302,6 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, i
   epi.apply8(m, n, a, b);
 }
 
-#ifdef APH_EXPERIMENTS       // a measured-and-superseded kernel family: no BASELINE configuration launches it (the wave-specialised kernel takes every
-                             // shape it was tuned for); kept compilable for A/B runs only
-// ---- phased 256x256x64 kernel (cdna_hip_programming.md section 5.5, "8-phase" schedule) ----------------------
-// 8 waves as 2 (M) x 4 (N), 128x64 of C per wave, double-buffered 64 KiB stages.  A k-tile is worked off in FOUR
-// phases, one C quadrant of the wave (64x32, 16 MFMAs over K = 64) each, in the order (A0,B0) (A0,B1) (A1,B1) (A1,B0)
-// so that consecutive phases share one operand's fragments: 24 ds_read_b128 feed 64 MFMAs.  A phase is
-//     { fragment reads + 2 DMA instructions | s_barrier | 16 MFMAs at raised priority | s_barrier }
-// and the waves of the second M half run ONE BARRIER BEHIND the first (`if (wr) s_barrier` up front): the two waves
-// that share a SIMD alternate, one in its MFMA segment while the other issues LDS reads and DMA.
-// The next k-tile streams in as four half-tiles (A0, B0, B1, A1: 16 KiB = 2 DMA instructions per wave each), one per
-// phase, each >= 3 phases ahead of its first read; counted vmcnt(4) keeps the newest two in flight.
-// Hazards.  RAW: the half-tile read in phase p+1 was issued in phase p-2; every wave retires its share (vmcnt(4):
-// only the issues of phases p-1 and p may be outstanding) before the barrier that precedes those reads -- for the
-// leading group that is the phase's second barrier, for the trailing group (one barrier behind) its first.
-// WAR: a stage is refilled during the k-tile after the one it served, >= 2 phases after the trailing group's last
-// read of the half-tile being replaced (B0 is kept in registers for phase 4, so phase 4 reads nothing).
-struct Gemm8 {
-  static constexpr int BM = 256, BN = 256, NTHREAD = 512, NWAVE = 8;
-  static constexpr int STAGE = (BM + BN) * GEMM_BK;      // halfs
-  static constexpr int SMEM = 2 * STAGE * 2;             // bytes (128 KiB)
-  static constexpr int CT_LD = 64 + 4, EP_MT = 2;
-};
-
-__device__ __forceinline__ void phase_barrier(bool wait, bool last) {
-  // `wait`: this wave's DMA shares for the next phase's reads must have landed (see RAW above)
-  if (!wait) wait_vm_barrier<63>();
-  else if (last) wait_vm_barrier<0>();
-  else wait_vm_barrier<4>();
-}
-
-template <class Epi, bool M32 = false>
-__global__ __launch_bounds__(512) void gemm8_f16_kernel(const half_t* __restrict__ A, int lda, const half_t* __restrict__ Bt, int ldb,
-                                                        int M, int N, int K, Epi epi, int ntiles) {
-  using C = Gemm8;
-  APH_DYN_SMEM(smem);
-  half_t* lds = reinterpret_cast<half_t*>(smem);
-  const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  // PERSISTENT TILE LOOP.  The grid is min(ntiles, CUs) workgroups (one per CU: 128 KiB of LDS); workgroup b runs on XCD
-  // b % 8 (observed dispatch, speed only).  XCD x owns one contiguous run of tiles (n-tiles fastest, so the tiles in flight
-  // on one L2 share A panels); its workgroups walk that run with stride = workgroups on the XCD.  With gridDim.x == ntiles
-  // this is the one-tile-per-workgroup order of the ring kernels.  Bijective for any grid size.
-  int tile, tile_end, tile_step;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x, G = nwg < 8 ? nwg : 8;      // G = 8 on the device whenever ntiles >= 8
-    const int q = ntiles / G, r = ntiles - q * G, xcd = b % G;
-    const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    tile_end = start + q + (xcd < r ? 1 : 0);
-    tile_step = (nwg - xcd + G - 1) / G;
-    tile = start + b / G;
-  }
-  const int ntn = N / C::BN;
-  // DMA shares: half-tile X, instruction i of this wave covers 8 consecutive tile rows starting at row0(X, i)
-  const int lrow = lane >> 3, pc = lane & 7;
-  // operand addresses = wave-uniform base (SGPR pair: matrix + k offset) + a 32-bit per-lane byte offset (the instruction's
-  // saddr form): 6 VGPRs instead of 6 pointers, and no vector address arithmetic in the main loop
-  unsigned oA[2][2];            // [half][i]
-  unsigned oB[2];               // [i], half 0; half 1 = + 32 rows (folded into the scalar base)
-  int m0 = 0, n0 = 0;
-  auto setup = [&](int t) {     // operand offsets of tile t
-    const int tm = t / ntn;
-    n0 = (t - tm * ntn) * C::BN;
-    m0 = tm * C::BM;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int q0 = (wave * 2 + i) * 8;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int row = (q0 >> 6) * 128 + h * 64 + (q0 & 63) + lrow;
-        int am = m0 + row; am = am < M ? am : M - 1;
-        oA[h][i] = ((unsigned)am * (unsigned)lda + ((pc ^ ((row >> 1) & 7)) << 3)) * 2u;
-      }
-      const int brow = (q0 >> 5) * 64 + (q0 & 31) + lrow;
-      oB[i] = ((unsigned)(n0 + brow) * (unsigned)ldb + ((pc ^ ((brow >> 1) & 7)) << 3)) * 2u;
-    }
-  };
-  const char* Ab = reinterpret_cast<const char*>(A);
-  const char* Bb = reinterpret_cast<const char*>(Bt);
-  const size_t bhalf = (size_t)32 * ldb * 2;
-  auto issue_a = [&](int h, int kt, half_t* stage) {
-    const char* base_k = Ab + (size_t)kt * (GEMM_BK * 2);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) glds16(base_k + oA[h][i], stage + (((wave * 2 + i) >> 3) * 128 + h * 64 + (((wave * 2 + i) * 8) & 63)) * GEMM_BK);
-  };
-  auto issue_b = [&](int h, int kt, half_t* stage) {
-    const char* base_k = Bb + (size_t)kt * (GEMM_BK * 2) + (h ? bhalf : 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      glds16(base_k + oB[i], stage + C::BM * GEMM_BK + (((wave * 2 + i) >> 2) * 64 + h * 32 + (((wave * 2 + i) * 8) & 31)) * GEMM_BK);
-  };
-
-  // accumulators and fragments: 16x16x32 -> acc[8][4] f32x4, A [row tile 16][k32 step], B [half][col tile 16][k32 step];
-  //                             32x32x16 -> acc32[4][2] f32x16, A [row tile 32][k16 step], B [half][k16 step] (one 32-col tile per half)
-  f32x4 acc[M32 ? 1 : 8][M32 ? 1 : 4];
-  f32x16 acc32[M32 ? 4 : 1][M32 ? 2 : 1];
-  half8 fa[4][2], fb[2][2][2];
-  half8 ga[2][4], gb[2][4];
-  const int frow = M32 ? (lane & 31) : (lane & 15);
-  const int arow = wr * 128 + frow, brow = wc * 64 + frow, fchunk = M32 ? (lane >> 5) : (lane >> 4);
-  auto read_a = [&](int h, const half_t* stage) {
-    if constexpr (M32) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ga[t][u] = *reinterpret_cast<const half8*>(stage + lds_off(arow + h * 64 + t * 32, 2 * u + fchunk));
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) fa[t][ks] = *reinterpret_cast<const half8*>(stage + lds_off(arow + h * 64 + t * 16, ks * 4 + fchunk));
-    }
-  };
-  auto read_b = [&](int h, const half_t* stage) {
-    if constexpr (M32) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) gb[h][u] = *reinterpret_cast<const half8*>(stage + C::BM * GEMM_BK + lds_off(brow + h * 32, 2 * u + fchunk));
-    } else {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          fb[h][t][ks] = *reinterpret_cast<const half8*>(stage + C::BM * GEMM_BK + lds_off(brow + h * 32 + t * 16, ks * 4 + fchunk));
-    }
-  };
-  auto quadrant = [&](int ah, int bh) {
-    mfma_prio(1);
-    if constexpr (M32) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) acc32[ah * 2 + mt][bh] = mfma_32x32x16_f16(gb[bh][u], ga[mt][u], acc32[ah * 2 + mt][bh]);
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt) acc[ah * 4 + mt][bh * 2 + nt] = mfma_16x16x32_f16(fb[bh][nt][ks], fa[mt][ks], acc[ah * 4 + mt][bh * 2 + nt]);
-    }
-    mfma_prio(0);
-  };
-
-  const int nk = K / GEMM_BK;
-  const bool lead = wr == 0;
-  int base = 0;                                  // k-tile kt of the current tile lives in stage (base + kt) & 1
-  setup(tile);
-  issue_a(0, 0, lds); issue_b(0, 0, lds); issue_b(1, 0, lds); issue_a(1, 0, lds);
-  for (;;) {
-    if constexpr (M32) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc32[i][j][r] = 0.f;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    // k-tile 0 has landed (issued above, or under the previous tile's epilogue); the previous tile's staging reads and
-    // stores are behind every wave
-    wait_vm_barrier<0>();
-    if (!lead) wait_vm_barrier<63>();            // trailing group: one barrier behind from here on
-    for (int kt = 0; kt < nk; ++kt) {
-      half_t* cur = lds + ((base + kt) & 1) * C::STAGE;
-      half_t* nxt = lds + ((base + kt + 1) & 1) * C::STAGE;
-      const bool more = kt + 1 < nk;
-      // phase 1: quadrant (A0, B0)
-      read_a(0, cur); read_b(0, cur);
-      if (more) issue_a(0, kt + 1, nxt);
-      phase_barrier(!lead, !more);
-      quadrant(0, 0);
-      phase_barrier(lead, !more);
-      // phase 2: (A0, B1)
-      read_b(1, cur);
-      if (more) issue_b(0, kt + 1, nxt);
-      phase_barrier(!lead, !more);
-      quadrant(0, 1);
-      phase_barrier(lead, !more);
-      // phase 3: (A1, B1)
-      read_a(1, cur);
-      if (more) issue_b(1, kt + 1, nxt);
-      phase_barrier(false, false);
-      quadrant(1, 1);
-      phase_barrier(false, false);
-      // phase 4: (A1, B0) -- nothing to read
-      if (more) issue_a(1, kt + 1, nxt);
-      phase_barrier(!lead, false);
-      quadrant(1, 0);
-      phase_barrier(lead, false);
-    }
-    if (lead) wait_vm_barrier<63>();             // balance the trailing group's extra barrier
-    __syncthreads();                             // both stages are dead
-    // Next tile's k-tile 0 streams in UNDER this tile's epilogue: it goes to the stage that served k-tile nk-2; the accumulators
-    // are staged in the other one (k-tile nk-1's), so the two never meet.  The epilogue's stores drain while the next main
-    // loop runs out of L2.
-    base = (base + nk) & 1;
-    const int em0 = m0, en0 = n0;
-    const int next = tile + tile_step;
-    const bool has_next = next < tile_end;       // workgroup-uniform
-    if (has_next) {
-      setup(next);
-      half_t* st0 = lds + base * C::STAGE;
-      issue_a(0, 0, st0); issue_b(0, 0, st0); issue_b(1, 0, st0); issue_a(1, 0, st0);
-    }
-    if constexpr (M32) {
-      // one tile per workgroup only (launch_gemm8): padded staging from the start of the ring
-      float* ct = reinterpret_cast<float*>(smem) + wave * (C::EP_MT * 16 * C::CT_LD);
-#pragma unroll
-      for (int p0 = 0; p0 < 8; p0 += C::EP_MT) {
-        wave_lds_fence();
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<f32x4*>(ct + (lane & 31) * C::CT_LD + nt * 32 + 8 * g + 4 * (lane >> 5)) =
-                f32x4{acc32[p0 / 2][nt][4 * g], acc32[p0 / 2][nt][4 * g + 1], acc32[p0 / 2][nt][4 * g + 2], acc32[p0 / 2][nt][4 * g + 3]};
-        wave_lds_fence();
-#pragma unroll
-        for (int it = 0; it < C::EP_MT * 2; ++it) {
-          const int r = it * 8 + (lane >> 3), c8 = (lane & 7) * 8;
-          const f32x4 a = *reinterpret_cast<const f32x4*>(ct + r * C::CT_LD + c8);
-          const f32x4 b = *reinterpret_cast<const f32x4*>(ct + r * C::CT_LD + c8 + 4);
-          const int m = em0 + (wr * 8 + p0) * 16 + r;
-          if (m < M) epi.apply8(m, en0 + wc * 64 + c8, a, b);
-        }
-      }
-    } else {
-      // 8 KiB per wave inside the dead stage: 32 rows x 16 chunks of 16 bytes, chunk c of row r at c ^ (r & 15) (the
-      // 16 lanes of one accumulator column group hit 16 different chunks; a row's 8 readers too)
-      float* ct = reinterpret_cast<float*>(lds + (base ^ 1) * C::STAGE) + wave * (C::EP_MT * 16 * 64);
-#pragma unroll
-      for (int p0 = 0; p0 < 8; p0 += C::EP_MT) {
-        wave_lds_fence();
-#pragma unroll
-        for (int mt = 0; mt < C::EP_MT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) {
-            const int r = mt * 16 + (lane & 15);
-            *reinterpret_cast<f32x4*>(ct + r * 64 + (((nt * 4 + (lane >> 4)) ^ (r & 15)) << 2)) = acc[p0 + mt][nt];
-          }
-        wave_lds_fence();
-#pragma unroll
-        for (int it = 0; it < C::EP_MT * 2; ++it) {
-          const int r = it * 8 + (lane >> 3), j = (lane & 7) * 2;
-          const f32x4 a = *reinterpret_cast<const f32x4*>(ct + r * 64 + ((j ^ (r & 15)) << 2));
-          const f32x4 b = *reinterpret_cast<const f32x4*>(ct + r * 64 + (((j + 1) ^ (r & 15)) << 2));
-          const int m = em0 + (wr * 8 + p0) * 16 + r;
-          if (m < M) epi.apply8(m, en0 + wc * 64 + j * 4, a, b);
-        }
-      }
-    }
-    if (!has_next) break;
-    tile = next;
-  }
-}
-
-#endif  // APH_EXPERIMENTS
-
 // ---- epilogues: apply8 gets 8 consecutive columns n..n+7 of row m -------------------------------------------
 __device__ __forceinline__ void store_h4(half_t* p, float a, float b, float c, float d) {
   half4 h = {(half_t)a, (half_t)b, (half_t)c, (half_t)d};
@@ -750,32 +487,15 @@ inline int gemm_persistent_wgs() {
 #endif
 }
 
-// the phased kernel addresses its operands with 32-bit byte offsets from the matrix base
-inline bool gemm8_addressable(int M, int lda, int N, int ldb) {
+// the wave-specialised and register-staged kernels address their operands with 32-bit byte offsets from the matrix base
+inline bool gemm_addressable32(int M, int lda, int N, int ldb) {
   return (size_t)M * lda * 2 < ((size_t)1 << 32) && (size_t)N * ldb * 2 < ((size_t)1 << 32);
 }
 
-#ifdef APH_EXPERIMENTS
-template <class Epi>
-inline void launch_gemm8(const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st) {
-  const int ntiles = (N / Gemm8::BN) * ((M + Gemm8::BM - 1) / Gemm8::BM);
-  if (gemm_mfma32()) {
-    APH_ALLOW_SMEM((gemm8_f16_kernel<Epi, true>), Gemm8::SMEM);
-    APH_LAUNCH((gemm8_f16_kernel<Epi, true>), dim3(ntiles), dim3(Gemm8::NTHREAD), Gemm8::SMEM, st, A, lda, Bt, ldb, M, N, K, epi, ntiles);
-  } else {
-    const int wgs = gemm_persistent_wgs();
-    APH_ALLOW_SMEM((gemm8_f16_kernel<Epi, false>), Gemm8::SMEM);
-    APH_LAUNCH((gemm8_f16_kernel<Epi, false>), dim3(ntiles < wgs ? ntiles : wgs), dim3(Gemm8::NTHREAD), Gemm8::SMEM, st, A, lda, Bt, ldb, M, N, K,
-               epi, ntiles);
-  }
-}
-
-#endif  // APH_EXPERIMENTS
-
 // tile choice, from the measured sweep over the ViT-B shapes at 1/2/4/8-rank shard sizes (tools/exp/tune_table.py):
-//   256x256 phased   wide outputs with >= 400 such tiles (N = 3072 at full batch: 456; QKV's 342 tiles take the 256x128 path --
-//                    forcing every GEMM through 256x128 instead measured 136.1 vs 139.0 steps/s, profiles/r02_ab_mfma32.txt)
-//   256x128          >= 160 tiles
+//   256x128 wave-specialised persistent   >= gemm_ws_min_tiles() (160) tiles, N <= 4096, 32-bit addressable operands (vit_gemm_ws.h)
+//   64x64 register-staged split-K    small M of a small batch, see gemm_rs_mode() (vit_gemm_rs.h)
+//   256x128, 3-stage ring            >= 160 tiles that the wave-specialised kernel does not take
 //   128x128, 8 waves, 4-stage ring   >= 160 such tiles (half-batch shards with N = 768, wide outputs of small shards)
 //   64x64 (2 workgroups per CU)      everything smaller; split-K when only a handful of tiles exist
 template <class Epi>
@@ -787,7 +507,7 @@ inline int& gemm_ws_min_tiles() {
   return v;
 }
 
-// The register-staged kernels of vit_gemm_rs.h.  gemm_rs_mode(): 1 (default) = the split-K kernel for GEMMs of at most 128 rows over
+// The register-staged split-K kernel of vit_gemm_rs.h.  gemm_rs_mode(): 1 (default) = the split-K kernel for GEMMs of at most 128 rows over
 // K <= 1024 WHEN THE WHOLE BATCH IS THAT SMALL (SplitKSpace::small_batch, set by the ViT entry points from cuts x tokens: one or two cuts,
 // C1): one launch with an ordered in-kernel reduction instead of a split-K launch plus its reduce launch (C1 577 -> 726 steps/s).  Over
 // K = 3072 the two-pass split-K stays: its 48 workgroups pull the cold weight matrix through four times as many CUs (11.3 against 20 us,
@@ -796,7 +516,7 @@ inline int& gemm_ws_min_tiles() {
 // (DESIGN.md section 4 *Precision*): three summation orders of those few GEMMs gave 2.6e-4 / 7.6e-4 / 1.04e-3 in the split-precision mode
 // (profiles/r05_stress_rs_ab.txt, r05_stress_rs_dense.txt; against fp64 this kernel is the more accurate of the two), and the order with
 // the margin under north_star's 1e-3 is worth more than 0.7 % of a shard's step;
-// 2 = every shape the register-staged kernels address (the A/B switch of bench.py --vit-path rs and the test hook); 0 = off.
+// 2 = every shape the split-K register-staged kernel addresses (the A/B switch of bench.py --vit-path rs and the test hook); 0 = off.
 inline int& gemm_rs_mode() {
   static int v = 1;
   return v;
@@ -805,7 +525,7 @@ inline int& gemm_rs_mode() {
 // does launch_gemm hand this shape to the wave-specialised persistent kernel?
 inline bool gemm_takes_ws(int M, int lda, int N, int ldb) {
   const int big_tiles = (N / GemmBig::BN) * ((M + GemmBig::BM - 1) / GemmBig::BM);
-  return gemm_ws_min_tiles() > 0 && big_tiles >= gemm_ws_min_tiles() && N <= 4096 /* GemmWS::BIAS_MAX */ && gemm8_addressable(M, lda, N, ldb) && !gemm_mfma32();
+  return gemm_ws_min_tiles() > 0 && big_tiles >= gemm_ws_min_tiles() && N <= 4096 /* GemmWS::BIAS_MAX */ && gemm_addressable32(M, lda, N, ldb) && !gemm_mfma32();
 }
 template <class Epi>
 inline void launch_gemm(const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st,
@@ -815,8 +535,8 @@ inline void launch_gemm(const half_t* A, int lda, const half_t* Bt, int ldb, int
     launch_gemm_ws(A, lda, Bt, ldb, M, N, K, epi, st);
     return;
   }
-  if (gemm_rs_mode() && (gemm_rs_mode() > 1 || ((sp ? sp->small_batch : true) && M <= 128 && K <= 1024)) && gemm8_addressable(M, lda, N, ldb) && !gemm_mfma32() &&
-      launch_gemm_rs_auto(A, lda, Bt, ldb, M, N, K, epi, st, gemm_rs_mode() > 1))
+  if (gemm_rs_mode() && (gemm_rs_mode() > 1 || ((sp ? sp->small_batch : true) && M <= 128 && K <= 1024)) && gemm_addressable32(M, lda, N, ldb) && !gemm_mfma32() &&
+      launch_gemm_rs_auto(A, lda, Bt, ldb, M, N, K, epi, st))
     return;
   const int mid_tiles = (N / GemmMidDeep8::BN) * ((M + GemmMidDeep8::BM - 1) / GemmMidDeep8::BM);
   if (big_tiles >= 160) launch_gemm_cfg<GemmBig>(A, lda, Bt, ldb, M, N, K, epi, st);

@@ -1,4 +1,4 @@
-// Small-M fp16 GEMMs for the CLIP ViT linears (round 5), gfx950: operands staged through REGISTERS, no barrier in the main loop.
+// Small-M fp16 GEMM for the CLIP ViT linears (round 5), gfx950: operands staged through REGISTERS, no barrier in the main loop.
 //
 //   C[m][n] = sum_k A[m][k] * Bt[n][k]        same contract as vit_gemm.h
 //
@@ -17,15 +17,13 @@
 //     NO hand-counted vmcnt (the compiler's own counted waits cover the register loads); the four waves drift freely;
 //   * operands are swapped at the MFMA (weights as A fragment) and the weight rows of a 16-row tile are permuted through the load address so
 //     that lane l ends up with 4 NT CONSECUTIVE columns of token row l & 15: the epilogues are vit_gemm.h's apply8.
-// Two kernels:
+// The kernel:
 //   gemm_sk_kernel  64 x 64 tile per workgroup, the four waves SPLIT K (wave w owns the k-tiles w, w + 4, ...: whole 128-byte lines of every
 //                   operand row) and each accumulates the full tile; the four fp32 partials meet in LDS at the end and are summed in the
 //                   fixed order 0, 1, 2, 3 (bitwise reproducible).  Every operand byte is fetched once per workgroup.  For the long-K,
 //                   narrow-N shapes (out-proj, fc2, dfc1, dqkv, patch embedding).
-//   gemm_ar_kernel  64 rows x 64 NT columns per workgroup, the A block (64 x K, K <= 1024) RESIDENT in LDS as K / 32 k-step images, filled
-//                   once; wave w streams the weight rows of its own 16 NT columns.  Tiles run column-group-major so that an XCD's L2 holds
-//                   the weight rows its workgroups share.  For the wide-N, K = width shapes (QKV, fc1, dfc2, patch-embedding dgrad); the
-//                   fused block kernels of vit_block.h are this kernel with other prologues / epilogues.
+// (An A-resident 64 x 256 variant for the wide-N shapes was measured slower than the ring kernels inside the step at every shard size --
+// profiles/r05_gemm_rs_shapes.txt, r05_fused_v4_steps.txt -- and is not in the tree: DESIGN.md section 4.)
 #pragma once
 #include "vit_gemm.h"
 
@@ -137,7 +135,10 @@ __global__ __launch_bounds__(256) void gemm_sk_kernel(const half_t* __restrict__
     wave_lds_fence();
     frags(f[0], ring);
     rs_stamp(trace, 1);
-    // rolled steady state + unrolled tail (see ARStream::run: straight-line code of this length misses the instruction cache in the step)
+    // Steady state as a ROLLED loop of U k-steps per trip (every step of it requests a k-step: no load behind a condition, exact vmcnt
+    // bookkeeping), the last steps unrolled with compile-time conditions.  Fully unrolled, a loop of this length is kilobytes of straight-line
+    // code that a wave runs through once: in the step, where three dozen kernels take turns, that is an instruction-cache miss stream per
+    // launch (measured on the A-resident variant: 18-21 us in the step against 13 us back to back, profiles/r05_gemm_rs_shapes.txt).
     constexpr int U = (PD % 2) ? 2 * PD : PD;
     constexpr int NMAIN = NS > PD + 1 ? ((NS - PD - 1) / U) * U : 0;
     auto step = [&](int s, int u, bool more, bool req) {
@@ -206,290 +207,11 @@ inline void launch_gemm_sk(const half_t* A, int lda, const half_t* Bt, int ldb, 
   }
 }
 
-#ifdef APH_EXPERIMENTS       // measured slower than the ring kernels inside the step at every shard size (profiles/r05_gemm_rs_shapes.txt,
-                             // r05_fused_v4_steps.txt): compiled for A/B builds and the CPU interpreter only, not into the product library
-// ---- A-resident kernel ----------------------------------------------------------------------------------------------------------------
-// shared pieces (also used by vit_block.h): the resident A block is nks k-step images of [64 rows][64 bytes]; behind it every wave has two
-// private images of [16 NT weight rows][64 bytes].
-template <int NT>
-struct GemmAR {
-  static constexpr int BM = 64, BN = 64 * NT, NTHREAD = 256, KMAX = 1024;
-  static constexpr int WIMG = NT * 1024;                     // bytes of one weight k-step image of a wave
-  static constexpr int smem(int K) { return (K / 32) * 4096 + 4 * 2 * WIMG; }
-};
-
-// Fill the resident A block from a row-major f16 matrix: rowoff = byte offsets of this lane's loads of the rows 16 q + lrow (clamped by
-// the caller); wave w copies the k-steps w, w + 4, ...; six k-steps (24 loads) in flight per wave and batch.  NKS at compile time: for
-// NKS % 4 == 0 no load sits behind a run-time condition.
-template <int NKS>
-__device__ __forceinline__ void ar_fill_copy(char* a_img, const char* Ab, const unsigned (&rowoff)[4], int wave, const RSLane& L) {
-#pragma unroll
-  for (int b0 = 0; b0 < NKS; b0 += 24) {
-    half8 r[6][4];
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-      if (b0 + 4 * j + 3 < NKS || (b0 + 4 * j < NKS && b0 + 4 * j + wave < NKS)) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) r[j][q] = ldg8(Ab + rowoff[q] + (size_t)(b0 + 4 * j + wave) * 64);
-      }
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-      if (b0 + 4 * j + 3 < NKS || (b0 + 4 * j < NKS && b0 + 4 * j + wave < NKS)) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sts8(a_img + (b0 + 4 * j + wave) * 4096 + q * 1024 + L.wpos, r[j][q]);
-      }
-  }
-}
-
-// The weight stream of one wave: acc[mt][nt] += A block x (its 16 NT weight rows)^T over nks k-steps.  woff[nt]: byte offset of this
-// lane's load of tile nt (the weight row of tile row lrow, chunk lpc) from Bb.  prefetch() requests k-steps 0 .. PD - 1 so that they fly
-// during the caller's prologue; run() does the rest.
-template <int NT, int PD>
-struct ARStream {
-  half8 R[PD][NT];
-  __device__ __forceinline__ void request(int s, int d, const char* Bb, const unsigned (&woff)[NT]) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) R[d][nt] = ldg8(Bb + woff[nt] + (size_t)s * 64);
-  }
-  template <int NKS>
-  __device__ __forceinline__ void prefetch(const char* Bb, const unsigned (&woff)[NT]) {
-#pragma unroll
-    for (int d = 0; d < PD; ++d)
-      if (d < NKS) request(d, d, Bb, woff);
-  }
-  // NKS = K / 32 at COMPILE time: straight-line code, unconditional loads, exact vmcnt bookkeeping (see gemm_sk_kernel)
-  template <int NKS>
-  __device__ __forceinline__ void run(f32x4 (&acc)[4][NT], const char* a_img, char* wimg, const char* Bb, const unsigned (&woff)[NT], const RSLane& L) {
-    struct Frags { half8 t[4], w[NT]; };
-    Frags f[2];
-    auto stage = [&](char* img, int d) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) sts8(img + nt * 1024 + L.wpos, R[d][nt]);
-    };
-    auto frags = [&](Frags& fr, const char* img, int s) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) fr.t[mt] = lds8(a_img + s * 4096 + mt * 1024 + L.fpos);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) fr.w[nt] = lds8(img + nt * 1024 + L.fpos);
-    };
-    stage(wimg, 0);
-    if (PD < NKS) request(PD, 0, Bb, woff);
-    wave_lds_fence();
-    frags(f[0], wimg, 0);
-    // Steady state as a ROLLED loop of U k-steps per trip (every step of it requests a k-step: no load behind a condition, exact vmcnt
-    // bookkeeping), the last steps unrolled with compile-time conditions.  Fully unrolled, the loop was ~14 KiB of straight-line code that a
-    // wave runs through once: in the step, where three dozen kernels take turns, that is an instruction-cache miss stream per launch
-    // (18-21 us in the step against 13 us back to back: profiles/r05_gemm_rs_shapes.txt, r05_kernel_stats_s26_fused_v3.csv).
-    constexpr int U = (PD % 2) ? 2 * PD : PD;
-    constexpr int NMAIN = NKS > PD + 1 ? ((NKS - PD - 1) / U) * U : 0;
-    auto step = [&](int s, int u, bool more, bool req) {          // k-step s (register set / image parity by u = s mod U)
-      if (more) {
-        char* img = wimg + ((u + 1) & 1) * (NT * 1024);
-        wave_lds_fence();
-        stage(img, (u + 1) % PD);
-        if (req) request(s + 1 + PD, (u + 1) % PD, Bb, woff);
-        wave_lds_fence();
-        frags(f[(u + 1) & 1], img, s + 1);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma_16x16x32_f16(f[u & 1].w[nt], f[u & 1].t[mt], acc[mt][nt]);
-    };
-#pragma unroll 1
-    for (int s0 = 0; s0 < NMAIN; s0 += U) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) step(s0 + u, u, true, true);
-    }
-#pragma unroll
-    for (int s = NMAIN; s < NKS; ++s) step(s, s % U, s + 1 < NKS, s + 1 + PD < NKS);
-  }
-};
-
-__device__ __forceinline__ void ar_tile(int ntm, int& tm, int& tn);
-// The same stream from FRAGMENT-MAJOR packed weights: Bp [column group][wave][k-step][tile nt][lane][8 halfs], lane l = tile row l & 15,
-// chunk l >> 4 -- a wave's load of one fragment is 1 KiB contiguous and lands in the registers the MFMA reads: no LDS staging of the weights.
-template <int NT, int PD>
-struct ARStreamP {
-  half8 R[PD][NT];
-  __device__ __forceinline__ void request(int s, int d, const char* Bw) {          // Bw: this wave's stream + lane * 16
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) R[d][nt] = ldg8(Bw + (size_t)(s * NT + nt) * 1024);
-  }
-  template <int NKS>
-  __device__ __forceinline__ void prefetch(const char* Bw) {
-#pragma unroll
-    for (int d = 0; d < PD; ++d)
-      if (d < NKS) request(d, d, Bw);
-  }
-  template <int NKS>
-  __device__ __forceinline__ void run(f32x4 (&acc)[4][NT], const char* a_img, const char* Bw, const RSLane& L) {
-    half8 t[2][4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) t[0][mt] = lds8(a_img + mt * 1024 + L.fpos);
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      if (s + 1 < NKS) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) t[(s + 1) & 1][mt] = lds8(a_img + (s + 1) * 4096 + mt * 1024 + L.fpos);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma_16x16x32_f16(R[s % PD][nt], t[s & 1][mt], acc[mt][nt]);
-      if (s + PD < NKS) request(s + PD, s % PD, Bw);
-    }
-  }
-};
-
-// Bt [N, K] row-major -> the packed image for column groups of 64 NT (one thread per 16-byte piece)
-template <int NT>
-__global__ void pack_frag_kernel(const half_t* __restrict__ Bt, half_t* __restrict__ Bp, int N, int K) {
-  const int nks = K / 32;
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)(N / 16) * nks * 64;
-  if (idx >= total) return;
-  const int lane = (int)(idx & 63);
-  size_t r = idx >> 6;
-  const int nt = (int)(r % NT); r /= NT;
-  const int ks = (int)(r % nks); r /= nks;
-  const int wave = (int)(r & 3), tn = (int)(r >> 2);
-  const int i = lane & 15, row = tn * 64 * NT + wave * 16 * NT + 4 * NT * (i >> 2) + 4 * nt + (i & 3);
-  *reinterpret_cast<half8*>(Bp + idx * 8) = *reinterpret_cast<const half8*>(Bt + (size_t)row * K + ks * 32 + (lane >> 4) * 8);
-}
-
-template <int NT, int NKS, int PD, class Epi>
-__global__ __launch_bounds__(256) void gemm_arp_kernel(const half_t* __restrict__ A, int lda, const half_t* __restrict__ Bp, int M, int N, Epi epi,
-                                                       unsigned long long* __restrict__ trace) {
-  using C = GemmAR<NT>;
-  APH_DYN_SMEM(smem);
-  rs_stamp(trace, 0);
-  const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
-  int tm, tn;
-  ar_tile((M + C::BM - 1) / C::BM, tm, tn);
-  const int m0 = tm * C::BM, n0 = tn * C::BN + wave * 16 * NT;
-  const RSLane L(lane);
-  const char* Bw = reinterpret_cast<const char*>(Bp) + ((size_t)(tn * 4 + wave) * NKS * NT * 64 + lane) * 16;
-  ARStreamP<NT, PD> W;
-  W.template prefetch<NKS>(Bw);
-  unsigned rowoff[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    int am = m0 + 16 * q + L.lrow;
-    am = am < M ? am : M - 1;
-    rowoff[q] = ((unsigned)am * (unsigned)lda + L.lpc * 8) * 2u;
-  }
-  ar_fill_copy<NKS>(smem, reinterpret_cast<const char*>(A), rowoff, wave, L);
-  rs_stamp(trace, 1);
-  __syncthreads();
-  rs_stamp(trace, 2);
-  f32x4 acc[4][NT];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  W.template run<NKS>(acc, smem, Bw, L);
-  rs_stamp(trace, 3);
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int m = m0 + 16 * mt + (lane & 15);
-    if (m < M) {
-#pragma unroll
-      for (int j = 0; j < NT / 2; ++j) epi.apply8(m, n0 + 4 * NT * (lane >> 4) + 8 * j, acc[mt][2 * j], acc[mt][2 * j + 1]);
-    }
-  }
-  rs_stamp(trace, 4);
-}
-
-// tile order of the A-resident kernels: column groups slowest, so that the contiguous run of an XCD holds few column groups (their weight
-// rows stay in its L2) and all row blocks of each
-__device__ __forceinline__ void ar_tile(int ntm, int& tm, int& tn) {
-  const int t = rs_tile_index();
-  tn = t / ntm;
-  tm = t - tn * ntm;
-}
-
-template <int NT, int NKS, int PD, class Epi>
-__global__ __launch_bounds__(256) void gemm_ar_kernel(const half_t* __restrict__ A, int lda, const half_t* __restrict__ Bt, int ldb, int M, int N,
-                                                      Epi epi, unsigned long long* __restrict__ trace) {
-  using C = GemmAR<NT>;
-  APH_DYN_SMEM(smem);
-  rs_stamp(trace, 0);
-  const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
-  constexpr int nks = NKS;
-  int tm, tn;
-  ar_tile((M + C::BM - 1) / C::BM, tm, tn);
-  const int m0 = tm * C::BM, n0 = tn * C::BN + wave * 16 * NT;        // this wave's first column
-  const RSLane L(lane);
-  const char* Ab = reinterpret_cast<const char*>(A);
-  const char* Bb = reinterpret_cast<const char*>(Bt);
-  unsigned woff[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)      // tile nt, tile row i = lrow is weight row 4 NT (i >> 2) + 4 nt + (i & 3) of the wave's 16 NT
-    woff[nt] = ((unsigned)(n0 + 4 * NT * (L.lrow >> 2) + 4 * nt + (L.lrow & 3)) * (unsigned)ldb + L.lpc * 8) * 2u;
-  ARStream<NT, PD> W;
-  W.template prefetch<NKS>(Bb, woff);                                         // the first weight k-steps fly during the fill
-  unsigned rowoff[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    int am = m0 + 16 * q + L.lrow;
-    am = am < M ? am : M - 1;
-    rowoff[q] = ((unsigned)am * (unsigned)lda + L.lpc * 8) * 2u;
-  }
-  ar_fill_copy<NKS>(smem, Ab, rowoff, wave, L);
-  rs_stamp(trace, 1);
-  __syncthreads();
-  rs_stamp(trace, 2);
-  f32x4 acc[4][NT];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  W.template run<NKS>(acc, smem, smem + nks * 4096 + wave * (2 * C::WIMG), Bb, woff, L);
-  rs_stamp(trace, 3);
-  // lane: token rows m0 + 16 mt + (lane & 15), columns n0 + 4 NT (lane >> 4) + 4 nt + r
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int m = m0 + 16 * mt + (lane & 15);
-    if (m < M) {
-#pragma unroll
-      for (int j = 0; j < NT / 2; ++j) epi.apply8(m, n0 + 4 * NT * (lane >> 4) + 8 * j, acc[mt][2 * j], acc[mt][2 * j + 1]);
-    }
-  }
-  rs_stamp(trace, 4);
-}
-
-template <int NT, int NKS, int PD, class Epi>
-inline void launch_gemm_ar_n(const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, Epi epi, hipStream_t st, unsigned long long* trace) {
-  using C = GemmAR<NT>;
-  const dim3 grid((N / C::BN) * ((M + C::BM - 1) / C::BM));
-  APH_ALLOW_SMEM((gemm_ar_kernel<NT, NKS, PD, Epi>), C::smem(NKS * 32));
-  APH_LAUNCH((gemm_ar_kernel<NT, NKS, PD, Epi>), grid, dim3(C::NTHREAD), C::smem(NKS * 32), st, A, lda, Bt, ldb, M, N, epi, trace);
-}
-// K = the width of a ViT (256 ... 1024): the block fits LDS
-inline bool gemm_ar_fits(int N, int K) { return N % GemmAR<4>::BN == 0 && (K == 256 || K == 512 || K == 768 || K == 1024); }
-template <int NT, int PD, class Epi>
-inline void launch_gemm_ar(const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st,
-                           unsigned long long* trace = nullptr) {
-  switch (K) {
-    case 256: launch_gemm_ar_n<NT, 8, PD>(A, lda, Bt, ldb, M, N, epi, st, trace); break;
-    case 512: launch_gemm_ar_n<NT, 16, PD>(A, lda, Bt, ldb, M, N, epi, st, trace); break;
-    case 768: launch_gemm_ar_n<NT, 24, PD>(A, lda, Bt, ldb, M, N, epi, st, trace); break;
-    default: launch_gemm_ar_n<NT, 32, PD>(A, lda, Bt, ldb, M, N, epi, st, trace); break;       // 1024
-  }
-}
-
-#endif  // APH_EXPERIMENTS
-
-// the split-K kernel if it is instantiated for this shape (false: the caller falls back to the ring kernels of vit_gemm.h); `wide`
-// (-DAPH_EXPERIMENTS builds): the A-resident kernel for wide outputs over K = width
+// the split-K kernel if it is instantiated for this shape (false: the caller falls back to the ring kernels of vit_gemm.h)
 template <class Epi>
-inline bool launch_gemm_rs_auto(const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st, bool wide) {
-#ifdef APH_EXPERIMENTS      // (the A-resident kernel behind every wide ViT GEMM: measured slower than the ring kernels in the step; A/B builds only)
-  if (wide && N >= 4 * GemmAR<4>::BN && gemm_ar_fits(N, K)) { launch_gemm_ar<4, 8>(A, lda, Bt, ldb, M, N, K, epi, st); return true; }
-#endif
-  (void)wide;
-  if (gemm_sk_fits(N, K)) launch_gemm_sk<4>(A, lda, Bt, ldb, M, N, K, epi, st);
-  else return false;
+inline bool launch_gemm_rs_auto(const half_t* A, int lda, const half_t* Bt, int ldb, int M, int N, int K, Epi epi, hipStream_t st) {
+  if (!gemm_sk_fits(N, K)) return false;
+  launch_gemm_sk<4>(A, lda, Bt, ldb, M, N, K, epi, st);
   return true;
 }
 

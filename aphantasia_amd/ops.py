@@ -281,7 +281,7 @@ class VitHandle:
 
 def gemm_f16(A, Bt, lib=None, tile_cfg=0):
     """C = A @ Bt^T (f16 in, f32 out); tile_cfg as in include/aphantasia_hip_test.h: 0 auto, 1 = 64x64, 2 = 256x128,
-    4 = 256x256 phased, 8 / 9 = 64x64 split-K x2 / x4, 10 = 128x128, 22 / 24 = 128x128 split-K x2 / x4"""
+    8 / 9 = 64x64 split-K x2 / x4, 10 = 128x128, 22 / 24 = 128x128 split-K x2 / x4"""
     L = _L(lib, A, Bt)
     M, K = A.shape
     N = Bt.shape[0]

@@ -16,8 +16,8 @@ int aph_vit_profile(aph_vit* vit, int on);
 int aph_vit_profile_read(aph_vit* vit, double* ms_total, long long* launches, double* flops);
 /* The ViT's attention kernels alone (head dim 64, T <= 256): mode 0 = forward (qkv -> att, lse), mode 1 = backward
  * ((qkv, att, lse, datt) -> dqkv).  qkv / dqkv [S*T, 3*heads*64] f16 (q | k | v column blocks), att / datt [S*T, heads*64] f16,
- * lse [S*heads*T] f32 (log-sum-exp of the scores / 8); d_delta: S*heads*T floats of scratch for the backward when T > 64 (only the two-kernel
- * backward of -DAPH_EXPERIMENTS builds writes it; still required for call compatibility). */
+ * lse [S*heads*T] f32 (log-sum-exp of the scores / 8); d_delta: unused and may be NULL (no kernel takes row-dot scratch; the argument stays
+ * so that the prototype does not change). */
 int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* d_delta, void* d_dqkv, int S, int T, int heads,
                   int mode, void* stream);
 /* C[M,N] f32 = A[M,K] f16 * Bt[N,K]^T f16 (N % 128 == 0, K % 64 == 0): the ViT GEMM core with the automatic tile choice */
@@ -29,7 +29,7 @@ int aph_gemm_f32_test(const float* d_A, int lda, int a_rowP, const float* d_Bt, 
 int aph_gemm_f16(const void* d_A, const void* d_Bt, int M, int N, int K, float* d_C, void* stream);
 /* same with explicit row pitches (elements, multiples of 8) and an explicit tile configuration:
  *    0  automatic (the shape heuristic of launch_gemm)
- *    1  64x64, 4 waves            2  256x128, 8 waves, 3-stage ring       4  256x256 phased (N % 256 == 0; -DAPH_EXPERIMENTS builds only)
+ *    1  64x64, 4 waves            2  256x128, 8 waves, 3-stage ring
  *    5  256x128 wave-specialised persistent (2 DMA producer waves + 8 MFMA consumer waves, register epilogue: vit_gemm_ws.h)
  *    8 / 9   64x64 split-K x2 / x4                10  128x128, 8 waves, 4-stage ring
  *   11  128x128, 4 waves, 2-stage ring, two workgroups per CU (measured slower than 2 on every ViT shape: profiles/r02_gemm_shapes.txt)
@@ -37,12 +37,11 @@ int aph_gemm_f16(const void* d_A, const void* d_Bt, int M, int N, int K, float* 
  *   14 / 15  64x64 register-staged split-K: each of the four waves streams its own k-tiles (global_load_dwordx4 -> private LDS image ->
  *            fragments; 4 / 3 k-steps of 32 in flight), no barrier in the main loop, ordered 4-way sum at the end (vit_gemm_rs.h: the small-M
  *            default for narrow outputs)
- *   16 / 17  64x256 A-resident: the 64 x K block of A stays in LDS, every wave streams the weight rows of its 64 columns (8 / 4 k-steps in
- *            flight); needs N % 256 == 0 and K = 256 ... 1024.  -DAPH_EXPERIMENTS builds only (measured slower than 1 / 10 in the step)
  *   22 / 24  128x128 split-K x2 / x4
- * | 0x100 (with 2, 4 or 5 only): measurement variant whose epilogue keeps the accumulators live but never stores (upper bound of
+ * | 0x100 (with 2 or 5 only): measurement variant whose epilogue keeps the accumulators live but never stores (upper bound of
  *   what overlapping the store phase could gain: tools/exp/gemm_nostore.py).
- * any other value is rejected (APH_ERR_ARG). */
+ * any other value is rejected (APH_ERR_ARG, the message names tile_cfg) before anything is launched -- 4 (the phased 256x256 kernel) and
+ * 16 / 17 (the A-resident 64x256 kernel) among them: those families lost their measurements and are no longer in the library. */
 int aph_gemm_f16_ld(const void* d_A, int lda, const void* d_Bt, int ldb, int M, int N, int K, float* d_C, int tile_cfg,
                     void* stream);
 
@@ -88,8 +87,8 @@ int aph_ln_test(int mode, int D, int M, int T, int xs, int res_T, int flags, con
  * runs: every switch here is an explicit call.) */
 int aph_crop_adjoint_set_gather(int on);
 /* Launch shape of the separable crop adjoint: rows per workgroup (rb), columns per thread (cpt), cuts per batch (nbc), column segments (nseg),
- * row-block order (0 = top-down, 1 = centre-out); 0 (order: -1) = automatic.  Shapes other than the shipped ones need a -DAPH_EXPERIMENTS build
- * (tools/exp/crop_adjoint_sweep.py). */
+ * row-block order (0 = top-down, 1 = centre-out); 0 (order: -1) = automatic.  The kernel is instantiated for 12 or 16
+ * accumulator rows (rb <= 12 / rb <= 16) x 2 or 3 columns per thread (tools/exp/crop_adjoint_sweep.py sweeps exactly those). */
 int aph_crop_adjoint_set_shape(int rb, int cpt, int nbc, int nseg, int order);
 
 /* MFMA shape of the main loops of the GEMM TEST ENTRIES (aph_gemm_f16, aph_gemm_f16_ld; the ViT's own GEMMs are compiled for the default
@@ -128,8 +127,8 @@ int aph_mfma_rate(int blocks, int iters, const void* d_src, float* d_out, void* 
 int aph_gemm_ws_probe(const void* d_A, const void* d_Bt, int M, int N, int K, void* d_out, void* d_out2, const float* d_bias, int epi_kind,
                       unsigned long long* d_trace, void* stream);
 
-/* The register-staged small-M GEMMs (tile_cfg 14 / 16) with an f16 output and per-phase stamps of the chip-wide 100 MHz clock
- * (tools/exp/gemm_rs_trace.py): kind 0 = split-K (1 = A-resident, 2 = A-resident from fragment-major weights: -DAPH_EXPERIMENTS builds);
+/* The register-staged split-K small-M GEMM (tile_cfg 14) with an f16 output and per-phase stamps of the chip-wide 100 MHz clock
+ * (tools/exp/gemm_rs_trace.py): kind must be 0 (any other kind is rejected with APH_ERR_ARG before anything is launched);
  * d_trace: (workgroups x 8) uint64 or NULL. */
 int aph_gemm_rs_probe(const void* d_A, const void* d_Bt, int M, int N, int K, void* d_out, int kind, unsigned long long* d_trace, void* stream);
 

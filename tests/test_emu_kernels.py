@@ -116,9 +116,6 @@ def test_gemm(emu):
     # flight): two to eight k-steps per wave (the two images and the register sets wrap), ragged M
     for cfg in (14, 15):
         K.check_gemm(emu, 'cpu', [(100, 128, 256), (130, 256, 2304), (70, 128, 768), (33, 384, 1024)], tile_cfg=cfg, variants=(0,))
-    # A-resident (16 / 17: 8 / 4 weight k-steps in flight): as many k-steps as the prefetch depth (K = 256) and more, ragged M, two column groups
-    for cfg in (16, 17):
-        K.check_gemm(emu, 'cpu', [(100, 256, 256), (130, 512, 512), (70, 256, 768), (33, 512, 1024)], tile_cfg=cfg, variants=(0,))
     # panel-grouped tile order (groups of 2 / 4 row panels, ragged last group: 3 and 5 panels)
     for g in (2, 4):
         prev = emu.cdll.aph_gemm_set_ws_pgroup(g)
@@ -183,25 +180,6 @@ def test_vit_split_precision_needs_enable_hilo(emu):
         emu.call('aph_vit_set_weight', vit.handle, k.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size)
     enc2, enc2_plain = vit.forward(hilo, 2, hilo=True).clone(), vit.forward(ops.patchify(x, p, lib=emu), 2).clone()
     assert not torch.equal(enc2, enc) and (enc2 - enc2_plain).abs().max().item() < 3e-3 * enc2_plain.abs().max().item()
-
-
-@pytest.mark.parametrize('fattn', [0, 2])
-def test_vit_fused_forward_blocks(emu, fattn):
-    """csrc/vit_block.h: LayerNorm inside the QKV / fc1 launches (DPP-row prologue into the resident A block), with (2) and without (0) the
-    attention behind the (cut, head) QKV GEMM; T = 5 (one ragged tile), 17 (two row blocks of the flat kernel at S = 5) and 50 tokens.
-    The same switch turns the fused BACKWARD on (a block's closing ln_1 input-gradient as the prologue of the next block's fc2 dgrad,
-    fp32 stream handed over through a second buffer; the last block's class-rows-only residual included): check_vit covers both"""
-    prev = emu.cdll.aph_vit_set_fused_max_rows(1 << 30)
-    prev_a = emu.cdll.aph_vit_set_fused_attn(fattn)
-    try:
-        K.check_vit(emu, 'cpu', check_fuse=False)
-        cfg = dict(input_resolution=64, patch_size=16, width=256, layers=2, heads=4, output_dim=128)      # T = 17
-        K.check_vit(emu, 'cpu', cfg, S=5, check_fuse=False)
-        cfg = dict(input_resolution=112, patch_size=16, width=256, layers=2, heads=4, output_dim=128)     # T = 50
-        K.check_vit(emu, 'cpu', cfg, S=2, check_fuse=False)
-    finally:
-        emu.cdll.aph_vit_set_fused_max_rows(prev)
-        emu.cdll.aph_vit_set_fused_attn(prev_a)
 
 
 def test_vit_split_precision_forward(emu):

@@ -216,7 +216,7 @@ def test_vit_forced_through_the_wave_specialised_gemm():
 
 
 def test_gemm_register_staged_small_m_vs_matmul_and_reproducible():
-    """tile_cfg 14 / 15 (split-K; and 16 / 17, A-resident, in -DAPH_EXPERIMENTS builds), vit_gemm_rs.h: the small-M kernels -- every wave stages its own operand stream
+    """tile_cfg 14 / 15 (split-K), vit_gemm_rs.h: the small-M kernel -- every wave stages its own operand stream
     through registers and a private LDS image with no barrier in the main loop.  The ViT-B shapes at the shard sizes of 8 / 4 / 2 ranks,
     ragged and single-k-tile cases against fp32 matmul, and the SAME BITS on every launch next to uneven load"""
     import torch
@@ -224,12 +224,8 @@ def test_gemm_register_staged_small_m_vs_matmul_and_reproducible():
     for cfg in (14, 15):
         K.check_gemm(None, DEV, [(1200, 768, 768), (1200, 768, 3072), (1150, 768, 2304), (2400, 768, 3072), (50, 768, 768), (50, 768, 3072),
                                  (70, 128, 256), (333, 256, 1024), (4750, 768, 2304)], tile_cfg=cfg, variants=(0,))
-    for cfg in ((16, 17) if _ffi.lib().experiments else ()):
-        K.check_gemm(None, DEV, [(1200, 2304, 768), (1200, 3072, 768), (24, 3072, 768), (50, 2304, 768), (70, 256, 256), (333, 512, 512),
-                                 (4750, 2304, 768), (2150, 3072, 768), (100, 1024, 1024)], tile_cfg=cfg, variants=(0,))
     g = torch.Generator().manual_seed(11)
-    for (M, N, Kd, cfgs) in ((1200, 768, 3072, (14, 15)), (2150, 768, 2304, (14, 15)), (50, 768, 3072, (14, 15))) + \
-            (((1200, 2304, 768, (16, 17)), (50, 3072, 768, (16, 17))) if _ffi.lib().experiments else ()):
+    for (M, N, Kd, cfgs) in ((1200, 768, 3072, (14, 15)), (2150, 768, 2304, (14, 15)), (50, 768, 3072, (14, 15))):
         A = torch.randn(M, Kd, generator=g).half().to(DEV); Bt = torch.randn(N, Kd, generator=g).half().to(DEV)
         for cfg in cfgs:
             ref = ops.gemm_f16(A, Bt, tile_cfg=cfg).clone()
@@ -238,39 +234,6 @@ def test_gemm_register_staged_small_m_vs_matmul_and_reproducible():
                 if i % 3 == 0:
                     busy = busy * 1.0001          # uneven load next to the launches
                 assert torch.equal(ops.gemm_f16(A, Bt, tile_cfg=cfg), ref), (M, N, Kd, cfg, i)
-
-
-@pytest.mark.parametrize('fattn', [0, 2])
-def test_vit_fused_forward_blocks(fattn):
-    """csrc/vit_block.h on hardware: tiny and ViT-B/32-shaped models through the fused forward (LayerNorm inside the QKV / fc1 launches,
-    with and without the attention behind the QKV GEMM) against the fp32 oracle, and bit-identical on repetition"""
-    import torch
-    from aphantasia_amd import _ffi, ops
-    from aphantasia_amd.weights import synthetic_visual_weights
-    L = _ffi.lib()
-    if not L.experiments:
-        pytest.skip('the fused block kernels were measured slower than the per-operator path at every shard size (profiles/r05_fused_v4_steps.txt) and are '
-                    'compiled into -DAPH_EXPERIMENTS builds only; they passed on hardware in profiles/r05_gpu_tests_fused_blocks.log and run under '
-                    'the CPU interpreter in tests/test_emu_kernels.py')
-    prev = L.cdll.aph_vit_set_fused_max_rows(1 << 30)
-    prev_a = L.cdll.aph_vit_set_fused_attn(fattn)
-    try:
-        K.check_vit(None, DEV, check_fuse=False)
-        cfg = dict(input_resolution=112, patch_size=16, width=256, layers=2, heads=4, output_dim=128)     # T = 50
-        K.check_vit(None, DEV, cfg, S=7, check_fuse=False)
-        from aphantasia_amd.weights import visual_config
-        cfg = visual_config('ViT-B/32')
-        K.check_vit(None, DEV, cfg, S=5, check_fuse=False, fwd_tol=5e-3, bwd_tol=3e-2)
-        w = synthetic_visual_weights(cfg, 3)
-        vit = ops.VitHandle(cfg, w, max_batch=24)
-        x = torch.randn(24, 3, 224, 224, generator=torch.Generator().manual_seed(5)).to(DEV)
-        patches = ops.patchify(x, 32)
-        ref = vit.forward(patches, 24).clone()
-        for _ in range(5):
-            assert torch.equal(vit.forward(patches, 24), ref)
-    finally:
-        L.cdll.aph_vit_set_fused_max_rows(prev)
-        L.cdll.aph_vit_set_fused_attn(prev_a)
 
 
 def test_gemm_splitk_matches_and_is_deterministic():

@@ -229,6 +229,21 @@ def test_gemm_epi_test_refuses_what_the_product_does_not_run(product_lib):
     assert call(kind=6, P=64, T=64) == -1 and call(kind=6, P=48, T=49) == -1      # T > P, M % P == 0
 
 
+def test_removed_gemm_families_are_refused(product_lib):
+    """the phased 256x256 kernel (tile_cfg 4) and the A-resident kernel (tile_cfg 16 / 17; probe kinds 1 / 2) are not in the library: on
+    shapes they used to take they are refused before any device work -- not routed to another kernel (the pointers are never dereferenced)"""
+    import ctypes
+    L = product_lib.cdll
+    p = ctypes.c_void_p(4096)
+    for cfg in (4, 16, 17, 4 | 0x100):
+        for (M, N, K) in ((1200, 3072, 768), (64, 256, 256)):
+            rc = L.aph_gemm_f16_ld(p, K, p, K, M, N, K, p, cfg, None)
+            assert rc < 0 and 'tile_cfg' in product_lib.last_error(), (cfg, M, N, K, rc, product_lib.last_error())
+    for kind in (1, 2):
+        rc = L.aph_gemm_rs_probe(p, p, 1200, 2304, 768, p, kind, None, None)
+        assert rc < 0 and 'kind' in product_lib.last_error(), (kind, rc, product_lib.last_error())
+
+
 def _uid_worker(rank, world, port, mode, q):
     import os
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))

@@ -1,6 +1,6 @@
 """Launch-shape sweep of the separable crop adjoint (crop_adjoint_rows_kernel) at the headline size: rows per workgroup x columns per thread x
-column segments x cuts per batch x row-block order, HIP-event timed through aph_sample_bwd with the same crop table.  Needs a
--DAPH_EXPERIMENTS build for the shapes the product library does not carry (`python -m aphantasia_amd._build --experiments`).
+column segments x cuts per batch x row-block order, HIP-event timed through aph_sample_bwd with the same crop table.  Sweeps the shapes the
+kernel is instantiated for: up to 16 rows per workgroup (12 or 16 accumulator rows), 2 or 3 columns per thread.
     python tools/exp/crop_adjoint_sweep.py [S] [H] [W] [patch]"""
 import os, sys
 import numpy as np, torch
@@ -41,11 +41,11 @@ L.cdll.aph_crop_adjoint_set_shape(0, 0, 0, 0, -1)
 run(); torch.cuda.synchronize()
 ref = grgb.clone()
 base = timeit()
-print('%dx%d, %d cuts, patch %d: automatic shape %.1f us (tap tables + adjoint; experiments build: %s)' % (W, H, S, P, base, L.experiments), flush=True)
+print('%dx%d, %d cuts, patch %d: automatic shape %.1f us (tap tables + adjoint)' % (W, H, S, P, base), flush=True)
 res = []
 for nseg in (1, 2, 3, 4):
-    for rb in ((4, 8, 9, 12, 16) if H <= 1080 else (12, 16, 20, 24)):
-        for cpt in (1, 2, 3):
+    for rb in ((4, 8, 9, 12, 16) if H <= 1080 else (12, 16)):
+        for cpt in (2, 3):
             xw = ((W + nseg - 1) // nseg + 3) & ~3
             nthr = ((xw + cpt - 1) // cpt + 63) // 64 * 64
             if nthr > 768 or (nthr < 256 and cpt > 1):

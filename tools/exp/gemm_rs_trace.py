@@ -1,4 +1,4 @@
-"""Where a workgroup's time goes inside the register-staged small-M GEMMs (aph_gemm_rs_probe: stamps of the chip-wide 100 MHz clock)."""
+"""Where a workgroup's time goes inside the register-staged split-K small-M GEMM (aph_gemm_rs_probe: stamps of the chip-wide 100 MHz clock)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from aphantasia_amd import _ffi
@@ -6,17 +6,13 @@ from aphantasia_amd.ops import ptr, _stream
 L = _ffi.lib()
 torch.manual_seed(0)
 for M in [int(m) for m in os.environ.get('MS', '1200,2400').split(',')]:
-    for (name, N, K, kind) in [('outproj', 768, 768, 0), ('fc2', 768, 3072, 0), ('dqkv', 768, 2304, 0), ('qkv', 2304, 768, 1), ('fc1', 3072, 768, 1), ('qkv packed', 2304, 768, 2), ('fc1 packed', 3072, 768, 2)]:
+    for (name, N, K, kind) in [('outproj', 768, 768, 0), ('fc2', 768, 3072, 0), ('dqkv', 768, 2304, 0)]:
         A = torch.randn(M, K, device='cuda').half(); B = torch.randn(N, K, device='cuda').half()
         o = torch.empty(M, N, device='cuda', dtype=torch.float16)
         st = _stream(A)
-        nwg = ((M + 63) // 64) * (N // (64 if kind == 0 else 256))
+        nwg = ((M + 63) // 64) * (N // 64)
         tr = torch.zeros(nwg * 8, dtype=torch.int64, device='cuda')
-        Bsrc = B
-        if kind == 2:
-            Bsrc = torch.empty_like(B)
-            L.call('aph_gemm_pack_frag', ptr(B), N, K, ptr(Bsrc), st)
-        f = lambda t: L.call('aph_gemm_rs_probe', ptr(A), ptr(Bsrc), M, N, K, ptr(o), kind, ptr(t) if t is not None else None, st)
+        f = lambda t: L.call('aph_gemm_rs_probe', ptr(A), ptr(B), M, N, K, ptr(o), kind, ptr(t) if t is not None else None, st)
         for _ in range(3): f(None)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -7,15 +7,12 @@ from aphantasia_amd.ops import ptr, _stream
 L = _ffi.lib()
 M = int(os.environ.get('M', 9500))
 SHAPES = [('qkv', M, 2304, 768), ('outproj/dout', M, 768, 768), ('fc1/dfc2', M, 3072, 768), ('fc2/dfc1', M, 768, 3072), ('dqkv', M, 768, 2304)]
-cfgs = [int(a) for a in sys.argv[1:]] or [0, 2, 4, 10]
+cfgs = [int(a) for a in sys.argv[1:]] or [0, 2, 10]
 for (name, M_, N, K) in SHAPES:
     A = torch.randn(M_, K, device='cuda').half(); B = torch.randn(N, K, device='cuda').half(); C = torch.empty(M_, N, device='cuda')
     st = _stream(A)
     line = '%-13s %5d x %5d x %5d :' % (name, M_, N, K)
     for cfg in cfgs:
-        if cfg == 4 and N % 256:
-            line += '   cfg4     --          '
-            continue
         f = lambda: L.call('aph_gemm_f16_ld', ptr(A), K, ptr(B), K, M_, N, K, ptr(C), cfg, st)
         for _ in range(3): f()
         torch.cuda.synchronize()

@@ -1,5 +1,5 @@
 """Sampler kernels alone at the headline size (1280x720, 190 cuts, ViT-B/32 patch layout): forward / adjoint timings for
--tf none and -tf fast, HIP events around the C-ABI calls.  APH_SAMPLER_DBG=<bits> selects ablation variants (experiments).
+-tf none and -tf fast, HIP events around the C-ABI calls.
     python tools/sampler_bench.py [S] [H] [W]"""
 import os, sys, time
 import numpy as np, torch
@@ -39,4 +39,4 @@ for name, trf in (('none', transforms.normalize()), ('fast', transforms.transfor
     prev = _ffi.lib().cdll.aph_crop_adjoint_set_gather(1)
     tb_old = timeit(b)
     _ffi.lib().cdll.aph_crop_adjoint_set_gather(prev)
-    print('-tf %-5s S=%d %dx%d dbg=%s: forward %7.1f us   adjoint %7.1f us  (with the round-2 gather crop adjoint: %7.1f us)' % (name, S, W, H, os.environ.get('APH_SAMPLER_DBG', '0'), timeit(f), tb_new, tb_old), flush=True)
+    print('-tf %-5s S=%d %dx%d: forward %7.1f us   adjoint %7.1f us  (with the round-2 gather crop adjoint: %7.1f us)' % (name, S, W, H, timeit(f), tb_new, tb_old), flush=True)
