@@ -193,7 +193,8 @@ __device__ __forceinline__ void at_fwd_tiles(const half_t* Qs, const half_t* Ks,
 }
 
 // qkv [M,3D] f16 -> att [M,D] f16, lse [S*heads*T] f32 (log-sum-exp of the scaled scores)
-__global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ att,
+// (`inline`: the one non-template kernel of this header, which two translation units include -- see vit_ops.h)
+inline __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ att,
                                                            float* __restrict__ lse, int T, int heads) {
   __shared__ __attribute__((aligned(16))) half_t lds[3 * 64 * 64];
   half_t* Qs = lds;
@@ -626,6 +627,64 @@ __global__ __launch_bounds__(512) void attn_bwd_one_g_kernel(const half_t* __res
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------------
+// host launchers: T <= 64 one-tile kernels, 64 < T <= 256 the blocked kernels (NB = ceil(T / 64))
+// ---------------------------------------------------------------------------------
+struct AttnArgs {
+  const half_t* qkv; half_t* att; float* lse;        // forward: qkv -> att, lse
+  const half_t* datt; half_t* dqkv;                  // backward: (qkv, att, lse, datt) -> dqkv
+  int S, T, heads;
+};
+template <int NB>
+void launch_attn_fwd_g(const AttnArgs& a, hipStream_t st) {
+  constexpr size_t smem = (size_t)2 * NB * 8192;
+  APH_ALLOW_SMEM((attn_fwd_mfma_g_kernel<NB>), smem);
+  APH_LAUNCH((attn_fwd_mfma_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem, st, a.qkv, a.att, a.lse, a.T, a.heads);
+}
+// blocked backward (64 < T <= 256): one kernel, P and dS formed once (attn_bwd_one_g_kernel)
+template <int NB>
+void launch_attn_bwd_g(const AttnArgs& a, hipStream_t st) {
+  constexpr size_t smem = (size_t)(4 + 2 * NB) * 8192 + 2 * 64 * sizeof(float);
+  APH_ALLOW_SMEM((attn_bwd_one_g_kernel<NB>), smem);
+  APH_LAUNCH((attn_bwd_one_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem, st, a.qkv, (const half_t*)a.att, a.datt, (const float*)a.lse, a.dqkv,
+             a.T, a.heads);
+}
+inline void launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
+  const int T = a.T;
+  if (T <= AT_T) APH_LAUNCH(attn_fwd_mfma_kernel, dim3(a.S * a.heads), dim3(256), 0, st, a.qkv, a.att, a.lse, T, a.heads);
+  else if (T <= 128) launch_attn_fwd_g<2>(a, st);
+  else if (T <= 192) launch_attn_fwd_g<3>(a, st);
+  else launch_attn_fwd_g<4>(a, st);
+}
+// workgroups of the persistent one-tile backward: 6 per CU (3 are resident at a time -- its LDS footprint; the second half starts as
+// the first finishes, which evens out the tail: measured 34.6 us one item per workgroup, 32.8 us with 3 per CU, 30.7 us with 6,
+// 31.8 with 8, 34.5 with 12 at C2, profiles/r02_attn_bwd_persistent.txt), never more than there are (cut, head) items
+inline int attn_bwd_wgs(int items) {
+#ifdef APH_EMU
+  return items < 3 ? items : 3;                     // exercises the item loop under the interpreter
+#else
+  constexpr int per_cu = 6;
+  thread_local int dev_cached = -1, ncu = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return items;
+  if (dev != dev_cached) {
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) return items;
+    dev_cached = dev;
+  }
+  const int w = ncu * per_cu;
+  return items < w ? items : w;
+#endif
+}
+inline void launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
+  const int T = a.T, items = a.S * a.heads;
+  // T <= 64: (the split dQ / dKdV kernels with NB = 1 were measured slower here: 7.62 vs 7.35 ms per C2 step)
+  if (T <= AT_RB) APH_LAUNCH(attn_bwd_mfma_kernel<AT_RB>, dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items);
+  else if (T <= AT_T) APH_LAUNCH(attn_bwd_mfma_kernel<AT_T>, dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items);
+  else if (T <= 128) launch_attn_bwd_g<2>(a, st);
+  else if (T <= 192) launch_attn_bwd_g<3>(a, st);
+  else launch_attn_bwd_g<4>(a, st);
 }
 
 }  // namespace aph

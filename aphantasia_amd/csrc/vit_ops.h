@@ -4,6 +4,8 @@
 // Follows openai/CLIP clip/model.py VisionTransformer / ResidualAttentionBlock (see
 // oracle/clip_vit_ref.py for the restatement these kernels are tested against).
 #pragma once
+#include <type_traits>
+
 #include "aph_device.h"
 
 namespace aph {
@@ -230,8 +232,10 @@ __global__ void ln_bwd_kernel(const void* __restrict__ dy, const float* __restri
 // threads (it was two): a thread's chain of dependent 16-load batches is 6 long instead of 24 -- the kernel is bound by that chain
 // (23 us for 1.5 MB of weights), not by bytes.  The eight partial sums of an output are added in slice order (deterministic).
 // ---------------------------------------------------------------------------------
+// (`inline` on the non-template kernels of this header: two translation units include it, and the host stub of a plain __global__ function
+// would be defined twice at link; a template's is not)
 constexpr int kHeadCuts = 4;
-__global__ __launch_bounds__(1024) void head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+inline __global__ __launch_bounds__(1024) void head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, const float* __restrict__ proj,
                                                        float* __restrict__ enc, int S, int T, int D, int E) {
   APH_DYN_SMEM(smem);
@@ -296,7 +300,7 @@ __global__ __launch_bounds__(1024) void head_fwd_kernel(const float* __restrict_
 // head backward: genc [S,E] -> the class-token rows of dx (fp32) and dx16; every other row of dx must have been zeroed
 // by the caller (only the class token reaches the head; the other rows of dx16 are not read before they are rewritten).  projT = proj transposed [E, D].
 // One workgroup per image, one thread per feature d (blockDim.x == D <= 1024).
-__global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict__ genc, const float* __restrict__ x,
+inline __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict__ genc, const float* __restrict__ x,
                                                        const float* __restrict__ gamma, const float* __restrict__ projT,
                                                        float* __restrict__ dx, half_t* __restrict__ dx16, int T, int D, int E) {
   APH_DYN_SMEM(smem);
@@ -326,6 +330,53 @@ __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict_
   const float v = rstd * (g - sg - xh * sgx);
   dx[(size_t)s * T * D + d] = v;
   dx16[(size_t)s * T * D + d] = (half_t)v;
+}
+
+// ---------------------------------------------------------------------------------
+// host launchers
+// ---------------------------------------------------------------------------------
+// f(std::integral_constant<int, NV>) for the run-time nv = D / 256 (1 ... 4)
+template <class F>
+inline void ln_with_nv(int nv, F&& f) {
+  switch (nv) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+// g2 / b2 / out2: the next LayerNorm of the same rows fused behind this one (ln_fwd_kernel)
+template <bool OUT_F16, bool CLS>
+void launch_ln_fwd(int nv, const float* x, const float* g, const float* b, void* out, int M, int T, const float* cls,
+                   const float* pos, float* x_fill, hipStream_t st, int xs = 1, const float* g2 = nullptr, const float* b2 = nullptr,
+                   half_t* out2 = nullptr, int hilo = 0) {
+  const dim3 grid((M + 3) / 4), block(256);
+  ln_with_nv(nv, [&](auto NV) { APH_LAUNCH((ln_fwd_kernel<decltype(NV)::value, OUT_F16, CLS>), grid, block, 0, st, x, g, b, out, M, T, cls, pos, x_fill, xs, g2, b2, out2, hilo); });
+}
+// res_T: residual on the rows with row % res_T == 0 only;  x_b / g_b: the previous LayerNorm's backward fused behind this one (ln_bwd_kernel)
+template <bool DY_F16, bool PATCH>
+void launch_ln_bwd(int nv, const void* dy, const float* x, const float* g, const void* res, float* out32, half_t* out16, int M,
+                   int T, hipStream_t st, int xs = 1, int res_T = 0, const float* x_b = nullptr, const float* g_b = nullptr, int res_f16 = 0) {
+  const dim3 grid((M + 3) / 4), block(256);
+  ln_with_nv(nv, [&](auto NV) { APH_LAUNCH((ln_bwd_kernel<decltype(NV)::value, DY_F16, PATCH>), grid, block, 0, st, dy, x, g, res, out32, out16, M, T, xs, res_T, x_b, g_b, res_f16); });
+}
+// x [S * T, D] (class rows read) -> enc [S, E]
+inline void launch_head_fwd(const float* x, const float* g, const float* b, const float* proj, float* enc, int S, int T, int D, int E, hipStream_t st) {
+  const size_t smem = sizeof(float) * kHeadCuts * (D + 8 * 128);
+  APH_ALLOW_SMEM(head_fwd_kernel, smem);
+  APH_LAUNCH(head_fwd_kernel, dim3((S + kHeadCuts - 1) / kHeadCuts, (E + 127) / 128), dim3(1024), smem, st, x, g, b, proj, enc, S, T, D, E);
+}
+
+// LayerNorm pairs of the first block as one kernel each way, and no zero fill of the fp32 gradient stream (aph_vit_set_fuse_ln(0): the
+// separate kernels -- bit-identical, kept for the equivalence test)
+inline int& vit_fuse_ln() {
+  static int v = 1;
+  return v;
+}
+// [r6] measurement switch (aph_vit_set_grad_stream_f16): the backward's residual-stream gradient kept in f16 only (see ln_bwd_kernel res_f16)
+inline int& vit_grad_stream_f16() {
+  static int v = 0;
+  return v;
 }
 
 }  // namespace aph

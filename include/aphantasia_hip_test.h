@@ -20,12 +20,12 @@ int aph_vit_profile_read(aph_vit* vit, double* ms_total, long long* launches, do
  * so that the prototype does not change). */
 int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* d_delta, void* d_dqkv, int S, int T, int heads,
                   int mode, void* stream);
-/* C[M,N] f32 = A[M,K] f16 * Bt[N,K]^T f16 (N % 128 == 0, K % 64 == 0): the ViT GEMM core with the automatic tile choice */
 /* the exact path's f32-input MFMA GEMM alone: C = epilogue(A * Bt^T), f32 in / out.  epi_kind 0 = plain (pitch ldc), 1 = + bias, 2 = QuickGELU
  * (C = g, d_aux = dg/du), 3 = GELU backward (C = acc * d_aux), 4 = residual (C = d_aux + acc + bias).  d_ws (ws_floats): split-K workspace or
  * NULL (never split).  a_rowP > 0: A row m is read from row m + m / a_rowP + 1 (the patch rows of a token-major buffer). */
 int aph_gemm_f32_test(const float* d_A, int lda, int a_rowP, const float* d_Bt, int ldb, int M, int N, int K, float* d_C, int ldc,
                       const float* d_bias, float* d_aux, int epi_kind, float* d_ws, size_t ws_floats, void* stream);
+/* C[M,N] f32 = A[M,K] f16 * Bt[N,K]^T f16 (N % 128 == 0, K % 64 == 0): the ViT GEMM core with the automatic tile choice */
 int aph_gemm_f16(const void* d_A, const void* d_Bt, int M, int N, int K, float* d_C, void* stream);
 /* same with explicit row pitches (elements, multiples of 8) and an explicit tile configuration:
  *    0  automatic (the shape heuristic of launch_gemm)
@@ -107,7 +107,7 @@ int aph_vit_set_grad_stream_f16(int on);
 /* Number of 256x128 output tiles from which the shape heuristic picks the wave-specialised persistent kernel (tile_cfg 5)
  * for the ViT's own GEMMs; 0 = never.  Process-wide, returns the previous value (A/B measurements, unit tests at small sizes). */
 int aph_gemm_set_ws_min_tiles(int tiles);
-/* Register-staged GEMMs (tile_cfg 14 / 16) inside the ViT: 1 (default) = the split-K kernel for GEMMs of at most 128 rows over K <= 1024
+/* Register-staged GEMMs (tile_cfg 14 / 15) inside the ViT: 1 (default) = the split-K kernel for GEMMs of at most 128 rows over K <= 1024
  * when the WHOLE batch of the ViT call is that small (cuts x tokens <= 128: one or two cuts) -- the class-row GEMMs of a larger batch's
  * last block stay on the two-pass split-K kernels; 2 = every shape below the wave-specialised kernel's threshold (A/B measurements),
  * 0 = never (the shared-ring tile configurations 1 / 2 / 10 and their two-pass split-K).  The stand-alone entries (aph_gemm_f16 with

@@ -294,17 +294,17 @@ LN_CASES = ['pre', 'pre_ln1', 'pre_ln1_hilo', 'ln_f16', 'ln_f16_hilo', 'ln_f16_c
 
 
 def check_layernorm(lib, dev, case, D, S=3, T=5, seed=0):
-    """One of the f16 path's LayerNorm launches (vit.hip) against fp64:
-      pre            ln_pre with class fill (x_fill = x0, as the ViT launches it), alone                           (vit.hip:592, fusion off)
-      pre_ln1[_hilo] the same fused with the first block's ln_1, f16 output ([hi | lo] rows)                        (vit.hip:592)
-      ln_f16[_hilo]  ln_1 / ln_2 with f16 output on all rows (xs = 1; hilo: ln_1 of the split-precision forward)     (vit.hip:606, 638)
-      ln_f16_cls     ln_2 of the last block on its class rows only (xs = T)                                         (vit.hip:638)
-      bwd_ln2        ln_2 backward, fp32 residual stream: res aliases out32 (res2 = dx), + the f16 copy             (vit.hip:704)
-      bwd_ln2_cls    the same on the class rows of the last block (xs = T)                                          (vit.hip:704)
-      bwd_ln2_f16    ln_2 backward with res_f16: res aliases out16, no fp32 stream, xs = T                          (vit.hip:703)
-      bwd_ln1_fused  ln_1 backward with res_T = T fused with ln_pre's backward (PATCH_ROWS output)                  (vit.hip:713)
-      bwd_ln1[_res_T] ln_1 backward unfused (res aliases out32), res_T = 0 / T                                      (vit.hip:717)
-      bwd_pre        ln_pre backward alone, f32 dy, PATCH_ROWS output                                               (vit.hip:719)
+    """One of the f16 path's LayerNorm launches (vit.hip; the launchers themselves are in vit_ops.h) against fp64:
+      pre            ln_pre with class fill (x_fill = x0, as the ViT launches it), alone                           (vit_forward_impl, fusion off)
+      pre_ln1[_hilo] the same fused with the first block's ln_1, f16 output ([hi | lo] rows)                        (vit_forward_impl)
+      ln_f16[_hilo]  ln_1 / ln_2 with f16 output on all rows (xs = 1; hilo: ln_1 of the split-precision forward)     (vit_forward_impl)
+      ln_f16_cls     ln_2 of the last block on its class rows only (xs = T)                                         (vit_forward_impl)
+      bwd_ln2        ln_2 backward, fp32 residual stream: res aliases out32 (res2 = dx), + the f16 copy             (vit_backward_impl)
+      bwd_ln2_cls    the same on the class rows of the last block (xs = T)                                          (vit_backward_impl)
+      bwd_ln2_f16    ln_2 backward with res_f16: res aliases out16, no fp32 stream, xs = T                          (vit_backward_impl)
+      bwd_ln1_fused  ln_1 backward with res_T = T fused with ln_pre's backward (PATCH_ROWS output)                  (vit_backward_impl)
+      bwd_ln1[_res_T] ln_1 backward unfused (res aliases out32), res_T = 0 / T                                      (vit_backward_impl)
+      bwd_pre        ln_pre backward alone, f32 dy, PATCH_ROWS output                                               (vit_backward_impl)
     M = S T rows (15 by default: not a multiple of the 4 rows of a workgroup); 16 guard rows behind every output.  Rows a launch must not
     read (class rows of x0 before ln_pre, rows between the class rows of an xs = T launch, residual rows outside res_T) hold NaN."""
     gen = torch.Generator().manual_seed(seed)
