@@ -11,6 +11,7 @@
 //   backward dKV (key block):   Q, dO, the block's K / V rows -> dK, dV   (reads lse and delta)
 // A wave works one row at a time: lane j holds the scores of keys j, j + 64, ... (<= 4); the row's probabilities go through a
 // per-wave LDS row, from which lane d forms output feature d.
+// (The kernels are `inline`: two translation units include this header -- the product and the test entries; see vit_ops.h.)
 #pragma once
 #include "aph_device.h"
 
@@ -34,7 +35,7 @@ __device__ __forceinline__ void atf_stage(const float* __restrict__ src, int ld,
   }
 }
 
-__global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ att, float* __restrict__ lse,
+inline __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ att, float* __restrict__ lse,
                                                            int T, int heads) {
   APH_DYN_SMEM(smem);
   const int nb = (T + kAtfRows - 1) / kAtfRows;
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
 }
 
 // dQ_i = 1/8 sum_j dS_ij K_j,  dS_ij = P_ij (dP_ij - delta_i),  dP_ij = dO_i . V_j,  P_ij = exp(S_ij / 8 - lse_i)
-__global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ datt, const float* __restrict__ lse,
+inline __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ datt, const float* __restrict__ lse,
                                                               float* __restrict__ delta, float* __restrict__ dqkv, int T, int heads) {
   APH_DYN_SMEM(smem);
   const int nb = (T + kAtfRows - 1) / kAtfRows;
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(const float* __res
 }
 
 // dK_j = 1/8 sum_i dS_ij Q_i,  dV_j = sum_i P_ij dO_i   (key block j0 .. j0 + kAtfRows)
-__global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ datt, const float* __restrict__ lse,
+inline __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ datt, const float* __restrict__ lse,
                                                                const float* __restrict__ delta, float* __restrict__ dqkv, int T, int heads) {
   APH_DYN_SMEM(smem);
   const int nb = (T + kAtfRows - 1) / kAtfRows;

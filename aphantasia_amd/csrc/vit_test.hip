@@ -10,6 +10,7 @@
 #include "vit_gemm_rs.h"
 #include "vit_ops.h"
 #include "vit_attn.h"
+#include "vit_attn_f32.h"
 #include "vit_gemm_f32.h"
 
 using namespace aph;
@@ -143,6 +144,19 @@ int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_da
   if (mode == 0) launch_attn_fwd(a, (hipStream_t)stream_);
   else launch_attn_bwd(a, (hipStream_t)stream_);
   return aph_check_launch("aph_attn_test");
+  APH_CATCH
+}
+
+// the exact path's fp32 attention launches (vit_attn_f32.h) alone; the backward takes no att
+int aph_attn_f32_test(const float* d_qkv, float* d_att, float* d_lse, const float* d_datt, float* d_delta, float* d_dqkv, int S, int T, int heads,
+                      int mode, void* stream_) {
+  APH_TRY
+  if (!d_qkv || !d_att || !d_lse || S < 1 || T < 1 || T > 256 || heads < 1 || (mode != 0 && mode != 1) ||
+      (mode == 1 && (!d_datt || !d_delta || !d_dqkv)))
+    return aph_fail(APH_ERR_ARG, "aph_attn_f32_test: bad argument");
+  if (mode == 0) launch_attn_fwd_f32(d_qkv, d_att, d_lse, S, T, heads, (hipStream_t)stream_);
+  else launch_attn_bwd_f32(d_qkv, d_datt, d_lse, d_delta, d_dqkv, S, T, heads, (hipStream_t)stream_);
+  return aph_check_launch("aph_attn_f32_test");
   APH_CATCH
 }
 

@@ -17,9 +17,16 @@ int aph_vit_profile_read(aph_vit* vit, double* ms_total, long long* launches, do
 /* The ViT's attention kernels alone (head dim 64, T <= 256): mode 0 = forward (qkv -> att, lse), mode 1 = backward
  * ((qkv, att, lse, datt) -> dqkv).  qkv / dqkv [S*T, 3*heads*64] f16 (q | k | v column blocks), att / datt [S*T, heads*64] f16,
  * lse [S*heads*T] f32 (log-sum-exp of the scores / 8); d_delta: unused and may be NULL (no kernel takes row-dot scratch; the argument stays
- * so that the prototype does not change). */
+ * so that the prototype does not change).  Of the backward kernels only the blocked one (T > 64) reads d_att (D_i = dO_i . att_i); the
+ * one-tile backward (T <= 64) forms D_i from the probabilities and never touches it -- the pointer must still not be NULL. */
 int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* d_delta, void* d_dqkv, int S, int T, int heads,
                   int mode, void* stream);
+/* The exact path's fp32 attention kernels alone (vit_attn_f32.h; head dim 64, T <= 256), every buffer f32 in the layouts above: mode 0 = forward
+ * (qkv -> att, lse), mode 1 = backward ((qkv, lse, datt) -> dqkv, and d_delta [S*heads*T] = sum_j P_ij dP_ij, which the dK / dV kernel reads
+ * back).  The backward does not read d_att.  Refused (APH_ERR_ARG) like aph_attn_test: NULL qkv / att / lse, S, T, heads < 1, T > 256, another
+ * mode, and in mode 1 a NULL d_datt, d_delta or d_dqkv. */
+int aph_attn_f32_test(const float* d_qkv, float* d_att, float* d_lse, const float* d_datt, float* d_delta, float* d_dqkv, int S, int T, int heads,
+                      int mode, void* stream);
 /* the exact path's f32-input MFMA GEMM alone: C = epilogue(A * Bt^T), f32 in / out.  epi_kind 0 = plain (pitch ldc), 1 = + bias, 2 = QuickGELU
  * (C = g, d_aux = dg/du), 3 = GELU backward (C = acc * d_aux), 4 = residual (C = d_aux + acc + bias).  d_ws (ws_floats): split-K workspace or
  * NULL (never split).  a_rowP > 0: A row m is read from row m + m / a_rowP + 1 (the patch rows of a token-major buffer). */

@@ -154,7 +154,8 @@ inline void launch(dim3 grid, dim3 block, size_t smem, const std::function<void(
     b->fibers.resize(nt);
     for (size_t i = old; i < (size_t)nt; ++i) b->fibers[i].stack = (char*)malloc(kStack);
   }
-  std::vector<char> dyn(smem + 64);
+  std::vector<char> dyn(smem + 64, (char)0xFF);      // dynamic LDS starts as NaN patterns (f16 0xFFFF, f32 0xFFFFFFFF): on the GPU it holds
+                                                     // whatever the last workgroup left, never the zeros a kernel might lean on
   b->dyn_smem = (char*)(((uintptr_t)dyn.data() + 63) & ~(uintptr_t)63);
   b->body = &body;
   b->nthreads = nt;

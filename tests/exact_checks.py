@@ -8,6 +8,7 @@ import torch
 from aphantasia_amd import _ffi, ops
 from aphantasia_amd.weights import synthetic_visual_weights
 from oracle import clip_vit_ref
+import vit_component_checks as V
 
 TINY = dict(input_resolution=32, patch_size=16, width=256, layers=2, heads=4, output_dim=128)
 
@@ -179,3 +180,126 @@ def check_sampler_f32(lib, dev, H=48, W=80, S=5, size=32, patch=16, augment=Fals
     a = ops.sample_bwd(geom, g.to(dev).contiguous(), table_d, aug_d, out_mode=_ffi.APH_OUT_NCHW_NORM, lib=lib)
     b = ops.sample_bwd(geom, g_pm, table_d, aug_d, out_mode=_ffi.APH_OUT_PATCH_F32, lib=lib)
     assert (a.cpu() - b.cpu()).abs().max().item() <= 1e-5 * a.abs().max().item()
+
+
+# ------------------------------------------------------------------------------------------------------------ fp32 attention (vit_attn_f32.h)
+def attn_f32_call(lib, qkv, att, lse, datt, delta, dqkv, S, T, heads, mode):
+    ops._L(lib, qkv).call('aph_attn_f32_test', ops.ptr(qkv), ops.ptr(att), ops.ptr(lse), ops.ptr(datt), ops.ptr(delta), ops.ptr(dqkv), S, T, heads,
+                          mode, ops._stream(qkv))
+
+
+def attn_fwd_bound_f32(r, v):
+    """(e_att, e_lse) of attn_fwd_f32_kernel; docstring of check_attention_f32"""
+    U = V.U
+    eps_p = (r['e_s'] + r['e_mx']) / 8 + U * (r['s'] - r['mx']).abs() / 8 + 2 * U
+    eps_l = (r['P'] * eps_p).sum(-1, keepdim=True) + 10 * U
+    e_att = (r['P'] * (eps_p + eps_l + 2 * U)) @ v.abs() + 1e-6 * (r['P'] @ v.abs())
+    ll = torch.log(r['l'])
+    e_lse = r['e_mx'] / 8 + eps_l + 2 * U * ll + U * (r['mx'].abs() / 8 + ll)
+    return e_att, e_lse
+
+
+def attn_bwd_bound_f32(r, b, L, q, k, dO, eps_extra=None):
+    """(e_D, e_dQ, e_dK, e_dV) of attn_bwd_dq_f32_kernel / attn_bwd_dkv_f32_kernel; docstring of check_attention_f32"""
+    U = V.U
+    eps_pb = r['e_s'] / 8 + U * (r['s'].abs() / 8 + L.abs()) + 2 * U
+    if eps_extra is not None:
+        eps_pb = eps_pb + eps_extra
+    Pb, dp = b['Pb'], b['dp']
+    e_D = (Pb * (eps_pb * dp.abs() + b['e_dp'])).sum(-1, keepdim=True) + 10 * U * (Pb * dp.abs()).sum(-1, keepdim=True)
+    dS8 = b['dS'].abs() * 8                                  # the kernels keep Pb (dp - D) and scale the contraction by 1 / 8
+    e_dS8 = dS8 * (eps_pb + 2 * U) + Pb * (b['e_dp'] + e_D)
+    e_dQ = (e_dS8 @ k.abs() + 1e-6 * (dS8 @ k.abs())) / 8
+    e_dK = (e_dS8.mT @ q.abs() + 1e-6 * (dS8.mT @ q.abs())) / 8
+    e_dV = (Pb * eps_pb).mT @ dO.abs() + 1e-6 * (Pb.mT @ dO.abs())
+    return e_D, e_dQ, e_dK, e_dV
+
+
+def check_attention_f32(lib, dev, S, T, heads, kind='normal', seed=0):
+    """The exact path's fp32 attention (vit_attn_f32.h) through aph_attn_f32_test against fp64 on the same inputs (the families of
+    vit_component_checks.attn_inputs, kept at their f16-representable values), element by element and per (cut, head): forward, the backward
+    alone (fed lse = f32(lse_ref)) and one chained run; delta too.  Sentinels behind every output, inputs unchanged, two identical calls give
+    the same bits.  Returns the worst err / bound per output ('dq+' ...: the chained run).
+
+    Every contraction is an fp32 fma chain, bounded by the figure check_gemm_f32 uses: e_s = 1e-6 |q| . |k| (scores), e_dp = 1e-6 |dO| . |v|,
+    1e-6 (P @ |v|) and the like for the output sums.  expf and logf: 1 ulp = 2 U (HIP's documented maximum).  U = 2^-24.
+    Forward (attn_fwd_f32_kernel):  p = expf((s - mx) * 0.125f): the difference of two computed scores, one rounding (the product is exact)
+      eps_p = (e_s + max_j e_s) / 8 + U |s - mx| / 8 + 2 U
+      eps_l = sum_j P eps_p + 10 U              l: at most 4 terms per lane and the 6 levels of wave_sum
+      e_att = (P (eps_p + eps_l + 2 U)) @ |v| + 1e-6 (P @ |v|)          P[j] = p * (1.0f / l): two roundings
+      e_lse = max_j e_s / 8 + eps_l + 2 U log l + U (|mx| / 8 + log l)   mx * 0.125f exact, logf, the sum
+    Backward (attn_bwd_dq_f32_kernel, attn_bwd_dkv_f32_kernel): Pb = expf(s * 0.125f - L) (no clamp), one rounding of the difference
+      eps_pb = e_s / 8 + U (|s| / 8 + |L|) + 2 U
+      e_D   = sum_j Pb (eps_pb |dp| + e_dp) + 10 U sum_j Pb |dp|         delta_i = sum_j Pb dp, summed like l; the dK / dV kernel reads it back
+      dS' = Pb (dp - D):  e_dS' = |dS'| (eps_pb + 2 U) + Pb (e_dp + e_D)
+      e_dQ = (e_dS' @ |k| + 1e-6 |dS'| @ |k|) / 8, e_dK likewise with |q|;  e_dV = (Pb eps_pb)^T @ |dO| + 1e-6 Pb^T @ |dO|
+    Chained: eps_pb += e_lse.  loss_scaled here means: |D_i| ~ 6.6e5 next to dp - D ~ 3e2, results finite and within the same bounds."""
+    D, M, NL, G = heads * 64, S * T, S * heads * T, V.GUARD_ROWS
+    what = 'fp32 attention %s S=%d T=%d heads=%d' % (kind, S, T, heads)
+    qkv, datt = (t.float() for t in V.attn_inputs(kind, S, T, heads, seed))
+    q, k, v = V.attn_items(qkv, S, T, heads, 3)
+    dO, = V.attn_items(datt, S, T, heads)
+    n_items = S * heads
+    step = max(1, V.ATTN_CHUNK // (T * T))
+    chunks = [slice(a, min(a + step, n_items)) for a in range(0, n_items, step)]
+    f32 = torch.float32
+
+    st = V.AttnStats()
+    O, e_att = torch.empty_like(q), torch.empty_like(q)
+    lse, e_lse = torch.empty(n_items, T, 1, dtype=torch.float64), torch.empty(n_items, T, 1, dtype=torch.float64)
+    for c in chunks:
+        r = V.attn_fwd_ref(q[c], k[c], v[c])
+        st.forward(r, T)
+        O[c], lse[c] = r['O'], r['lse']
+        e_att[c], e_lse[c] = attn_fwd_bound_f32(r, v[c])
+    st.check_forward(kind, what)
+
+    ins = dict(qkv=qkv, datt=datt)
+    dd = {n: t.clone().to(dev) for n, t in ins.items()}
+    held = {}
+
+    def fwd():
+        att, ls = V.sentinel(M + G, D, f32, dev), V.sentinel(1, NL + G, f32, dev)
+        attn_f32_call(lib, dd['qkv'], att, ls, None, None, None, S, T, heads, 0)
+        held['att'], held['lse'] = att, ls
+        return att.cpu(), ls.cpu()
+    lse_in = V.sentinel(1, NL + G, f32, 'cpu')
+    lse_in[0, :NL] = lse.reshape(-1).float()
+    att_nan = V.sentinel(M + G, D, f32, dev)                 # the backward takes no att: all NaN, and untouched afterwards
+
+    def bwd(ls):
+        l0 = V.bits(ls).clone()
+        dq, dl = V.sentinel(M + G, 3 * D, f32, dev), V.sentinel(1, NL + G, f32, dev)
+        attn_f32_call(lib, dd['qkv'], att_nan, ls, dd['datt'], dl, dq, S, T, heads, 1)
+        assert torch.equal(V.bits(ls), l0), what + ': the backward changed lse'
+        return dq.cpu(), dl.cpu()
+    att, ls = V._twice(fwd, what + ' forward')
+    g_alone, d_alone = V._twice(lambda: bwd(lse_in.clone().to(dev)), what + ' backward')
+    g_chain, d_chain = bwd(held['lse'])
+    V._unchanged(dd, ins, what)
+
+    fd = V.Findings(what)
+    fd.within('att', att[:M], V.attn_rows(O, S, T, heads), V.attn_rows(e_att, S, T, heads))
+    fd.within('lse', ls[0, :NL], lse.reshape(-1), e_lse.reshape(-1))
+    fd.run(V.assert_untouched, att, V._window(M + G, D, slice(0, M)), what + ' (att)')
+    fd.run(V.assert_untouched, ls, V._window(1, NL + G, (0, slice(0, NL))), what + ' (lse)')
+    fd.run(V.assert_untouched, att_nan.cpu(), torch.zeros(M + G, D, dtype=torch.bool), what + ' (att of the backward)')
+    L_in = lse_in[0, :NL].double().reshape(n_items, T, 1)
+    got = {'': V.attn_items(g_alone[:M], S, T, heads, 3), '+': V.attn_items(g_chain[:M], S, T, heads, 3)}
+    dl = {'': d_alone[0, :NL].reshape(n_items, T, 1), '+': d_chain[0, :NL].reshape(n_items, T, 1)}
+    for c in chunks:
+        r = V.attn_fwd_ref(q[c], k[c], v[c])
+        for tag in ('', '+'):
+            L = L_in[c] if tag == '' else r['lse']
+            b = V.attn_bwd_ref(r['s'], L, q[c], k[c], v[c], dO[c], clamp=False)
+            if tag == '':
+                st.backward(b)
+            e = attn_bwd_bound_f32(r, b, L, q[c], k[c], dO[c], eps_extra=None if tag == '' else e_lse[c])
+            fd.within('delta' + tag, dl[tag][c], b['D'], e[0])
+            for i, n in enumerate(('dQ', 'dK', 'dV')):
+                fd.within(n.lower() + tag, got[tag][i][c], b[n], e[1 + i])
+    st.check_backward(kind, what)
+    for tag, gq, gd in (('', g_alone, d_alone), ('+', g_chain, d_chain)):
+        fd.run(V.assert_untouched, gq, V._window(M + G, 3 * D, slice(0, M)), what + ' (dqkv%s)' % tag)
+        fd.run(V.assert_untouched, gd, V._window(1, NL + G, (0, slice(0, NL))), what + ' (delta%s)' % tag)
+    return fd.finish()

@@ -97,3 +97,20 @@ def test_clis_refuse_exact_with_precise():
     for mod in (clip_fft, illustrip):
         with pytest.raises(SystemExit):
             mod.get_args(['-t', 'x', '--exact', '--precise'])
+
+
+# ---- the fp32 attention kernels alone against fp64 (exact_checks.check_attention_f32): the kAtfRows = 32 row blocks (one row, a full block,
+# one row into the next), lanes' 64-key strides, and T = 256 -- the 156 KiB dynamic-LDS launch no ViT reaches (T = n^2 + 1 <= 226)
+def _show(tag, ratios):
+    print('%s: worst err / bound  %s' % (tag, '  '.join('%s %.3f' % kv for kv in ratios.items())))
+
+
+@pytest.mark.parametrize('T', [1, 31, 32, 33, 50, 64, 65, 197, 255, 256])
+def test_attention_f32_vs_fp64(emu, T):
+    _show('fp32 T=%d normal' % T, X.check_attention_f32(emu, 'cpu', S=2 if T <= 64 else 1, T=T, heads=2, seed=T))
+
+
+@pytest.mark.parametrize('T', [50, 197])
+@pytest.mark.parametrize('kind', [k for k in X.V.ATTN_KINDS if k != 'normal'])
+def test_attention_f32_families_vs_fp64(emu, kind, T):
+    _show('fp32 T=%d %s' % (T, kind), X.check_attention_f32(emu, 'cpu', S=1, T=T, heads=2, kind=kind, seed=3))

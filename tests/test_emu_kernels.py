@@ -289,3 +289,30 @@ def test_gemm_epilogue_class_rows(emu, tile_cfg, epi):
 @pytest.mark.parametrize('case', V.LN_CASES)
 def test_layernorm_vs_fp64(emu, case, D):
     V.check_layernorm(emu, 'cpu', case, D)
+
+
+# ---- the f16 attention kernels against fp64, element by element (vit_component_checks.check_attention_fp64): every tile, 32-key fragment
+# and 64-token block boundary -- one valid row, a full tile, one row into the next -- on the one-tile kernels (RB = 56: T <= 56, RB = 64) and
+# the blocked ones (NB = 2, 3, 4)
+ATTN_T = [1, 2, 15, 16, 17, 48, 49, 50, 56, 57, 63, 64, 65, 96, 97, 127, 128, 129, 160, 191, 192, 193, 197, 255, 256]
+
+
+def _show(tag, ratios):
+    print('%s: worst err / bound  %s' % (tag, '  '.join('%s %.3f' % kv for kv in ratios.items())))
+
+
+@pytest.mark.parametrize('T', ATTN_T)
+def test_attention_vs_fp64(emu, T):
+    """two heads (the head column offset); at T <= 64 two cuts: 4 (cut, head) items on the interpreter's 3 persistent workgroups"""
+    _show('T=%d normal' % T, V.check_attention_fp64(emu, 'cpu', S=2 if T <= 64 else 1, T=T, heads=2, seed=T))
+
+
+@pytest.mark.parametrize('T', [50, 64, 65, 197, 256])
+@pytest.mark.parametrize('kind', [k for k in V.ATTN_KINDS if k != 'normal'])
+def test_attention_families_vs_fp64(emu, kind, T):
+    _show('T=%d %s' % (T, kind), V.check_attention_fp64(emu, 'cpu', S=1, T=T, heads=2, kind=kind, seed=3))
+
+
+def test_attention_vs_fp64_item_loop(emu):
+    """10 (cut, head) items on 3 persistent workgroups (4 / 3 / 3 items each), two heads"""
+    _show('S=5 T=50 heads=2', V.check_attention_fp64(emu, 'cpu', S=5, T=50, heads=2, seed=7))

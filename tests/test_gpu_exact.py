@@ -158,3 +158,21 @@ def test_gemm_f32_full_shapes_vs_fp64():
     X.check_sampler_f32(L, DEV, augment=False)
     X.check_sampler_f32(L, DEV, augment=True)
     X.check_enable_f32_refusals(L, DEV)
+
+
+def _show(tag, ratios):
+    print('%s: worst err / bound  %s' % (tag, '  '.join('%s %.3f' % kv for kv in ratios.items())))
+
+
+@pytest.mark.parametrize('T', [1, 31, 32, 33, 50, 64, 65, 197, 255, 256])
+def test_attention_f32_vs_fp64(T):
+    """the fp32 attention kernels alone at 12 heads: the 32-row blocks' edges and T = 256, the 156 KiB dynamic-LDS launch no ViT reaches"""
+    L = __import__('aphantasia_amd._ffi', fromlist=['lib']).lib()
+    _show('fp32 T=%d normal' % T, X.check_attention_f32(L, DEV, S=3, T=T, heads=12, seed=T))
+
+
+@pytest.mark.parametrize('S,T', [(24, 50), (6, 197), (3, 256)])
+@pytest.mark.parametrize('kind', [k for k in X.V.ATTN_KINDS if k != 'normal'])
+def test_attention_f32_families_vs_fp64(kind, S, T):
+    L = __import__('aphantasia_amd._ffi', fromlist=['lib']).lib()
+    _show('fp32 S=%d T=%d %s' % (S, T, kind), X.check_attention_f32(L, DEV, S=S, T=T, heads=12, kind=kind, seed=5))

@@ -348,3 +348,25 @@ def test_gemm_epilogue_residual_at_stress_magnitude():
 @pytest.mark.parametrize('case', V.LN_CASES)
 def test_layernorm_vs_fp64(case, D):
     V.check_layernorm(None, DEV, case, D, S=49 if D == 768 else 3, T=50 if D == 768 else 5)
+
+
+# ---- the f16 attention kernels against fp64, element by element (vit_component_checks.check_attention_fp64)
+ATTN_T = [1, 2, 15, 16, 17, 48, 49, 50, 56, 57, 63, 64, 65, 96, 97, 127, 128, 129, 160, 191, 192, 193, 197, 255, 256]
+
+
+def _show(tag, ratios):
+    print('%s: worst err / bound  %s' % (tag, '  '.join('%s %.3f' % kv for kv in ratios.items())))
+
+
+@pytest.mark.parametrize('T', ATTN_T)
+def test_attention_vs_fp64(T):
+    """every tile / fragment / block boundary at 12 heads, 3 cuts: 36 (cut, head) items, fewer than the persistent backward's workgroups"""
+    _show('T=%d normal' % T, V.check_attention_fp64(None, DEV, S=3, T=T, heads=12, seed=T))
+
+
+@pytest.mark.parametrize('S,T', [(190, 50), (95, 197)])
+@pytest.mark.parametrize('kind', V.ATTN_KINDS)
+def test_attention_families_vs_fp64_product_shapes(kind, S, T):
+    """every input family at the product's shapes: ViT-B/32 at 190 cuts (2280 items: more than the persistent backward's workgroups, the item
+    loop) and ViT-B/16 at the 95 cuts of BASELINE configs[3] (400 samples x 0.25 x 0.95)"""
+    _show('S=%d T=%d %s' % (S, T, kind), V.check_attention_fp64(None, DEV, S=S, T=T, heads=12, kind=kind, seed=5))

@@ -196,6 +196,7 @@ def test_error_convention_on_bad_arguments(product_lib):
         'aph_grid_warp': lambda: L.aph_grid_warp(null, null, 3, 8, 8, ctypes.c_float(0.3), ctypes.c_float(0.0), ctypes.c_float(0.0), ctypes.c_float(0.5),
                                                  ctypes.c_float(0.05), null, null, null),
         'aph_attn_test': lambda: L.aph_attn_test(null, null, null, null, null, null, 1, 50, 12, 0, null),
+        'aph_attn_f32_test': lambda: L.aph_attn_f32_test(null, null, null, null, null, null, 1, 50, 12, 0, null),
         'aph_gemm_f16_epi_test': lambda: L.aph_gemm_f16_epi_test(null, 64, null, 64, 1, 128, 64, null, 128, null, null, null, ctypes.c_float(1.0), 1,
                                                                  0, 0, 0, null, ctypes.c_size_t(0), 1, null),
         'aph_ln_test': lambda: L.aph_ln_test(1, 256, 1, 1, 1, 0, 0, null, null, null, null, null, null, null, null, null, null, null, null, null, null),

@@ -455,3 +455,317 @@ def check_layernorm(lib, dev, case, D, S=3, T=5, seed=0):
     assert_within(o32[rows], want, e, what + ' (fp32 stream)')
     assert torch.equal(bits(o32[other]), bits(res[other])), what + ': fp32 stream changed outside the launch rows'
     assert_untouched(o16, _window(M + G, D, rows), what + ' (f16)')
+
+
+# ------------------------------------------------------------------------------------------------------------------------- attention
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+KSL = 0.125 * LOG2E              # kSL of vit_attn.h
+ATTN_KINDS = ('normal', 'flat', 'peaked', 'negative', 'loss_scaled', 'scaled_dO')
+ATTN_CHUNK = 6000000             # elements of one [items, T, T] fp64 temporary of the reference
+
+
+def attn_inputs(kind, S, T, heads, seed=0):
+    """qkv [S T, 3 D], datt [S T, D] f16 of one input family (D = 64 heads):
+      normal       randn * 1.5, datt = randn (check_attention's)
+      flat         q, k * 0.05: P about 1 / T, many probabilities with equal exponents
+      peaked       q, k = randn * 6 (the normal family's times 4): near one-hot rows, max_j P > 0.99 on 0.7 - 0.8 of them
+      negative     q = u + 0.1 n, k = -u + 0.1 n with one u = 1.25 randn(64) per head: every score negative, lse < 0 -- a padded key (score 0)
+                   would be the row maximum if the forward's mask were wrong, and at_p's clamp at 0 is what keeps the backward's p finite there
+                   (1.25: with twelve heads the smallest |u|^2 still leaves lse < 0 at T = 256, where log T = 5.5)
+      loss_scaled  the negative q / k, v_j = c + 0.05 n with c = +-16 per feature, dO_i = 40 c: |D_i| / 8 = 40 * 64 * 256 / 8 = 8.2e4 is past the
+                   f16 range while every valid dS and the gradient (~1e3) are far inside it
+      scaled_dO    normal with datt * 3000 (gradients ~1e4, still inside f16)"""
+    assert kind in ATTN_KINDS, kind
+    g = torch.Generator().manual_seed(seed)
+    D, M = heads * 64, S * T
+    qkv = torch.randn(M, 3 * D, generator=g) * 1.5
+    datt = torch.randn(M, D, generator=g)
+    if kind == 'flat':
+        qkv[:, :2 * D] *= 0.05
+    elif kind == 'peaked':
+        qkv[:, :2 * D] *= 4.0
+    elif kind == 'scaled_dO':
+        datt *= 3000.0
+    elif kind in ('negative', 'loss_scaled'):
+        u = 1.25 * torch.randn(1, D, generator=g)
+        qkv[:, :D] = u + 0.1 * torch.randn(M, D, generator=g)
+        qkv[:, D:2 * D] = -u + 0.1 * torch.randn(M, D, generator=g)
+        if kind == 'loss_scaled':
+            c = 16.0 * (torch.randint(0, 2, (1, D), generator=g) * 2 - 1).float()
+            qkv[:, 2 * D:] = c + 0.05 * torch.randn(M, D, generator=g)
+            datt = (40.0 * c).expand(M, D).contiguous()
+    return qkv.half(), datt.half()
+
+
+def attn_items(x, S, T, heads, parts=1):
+    """[S T, parts * heads * 64] rows -> `parts` fp64 tensors [S heads, T, 64], one (cut, head) item per leading index"""
+    x = x.double().reshape(S, T, parts, heads, 64)
+    return [x[:, :, i].permute(0, 2, 1, 3).reshape(S * heads, T, 64) for i in range(parts)]
+
+
+def attn_rows(x, S, T, heads):
+    """[S heads, T, 64] -> [S T, heads * 64]"""
+    return x.reshape(S, heads, T, 64).permute(0, 2, 1, 3).reshape(S * T, heads * 64)
+
+
+def attn_fwd_ref(q, k, v):
+    """fp64 attention of a chunk of items [n, T, 64] on the RAW scores s = q . k (the kernels scale by 1/8 inside the exponent):
+    e_s = 1e-6 |q| . |k| (the project's accumulator figure, check_gemm_epilogue), mx = max_j s, l = sum_j exp((s - mx) / 8), P, O = P v, lse"""
+    s = q @ k.mT
+    e_s = 1e-6 * (q.abs() @ k.abs().mT)
+    mx = s.amax(-1, keepdim=True)
+    pu = torch.exp((s - mx) / 8)
+    l = pu.sum(-1, keepdim=True)
+    P = pu / l
+    return dict(s=s, e_s=e_s, mx=mx, e_mx=e_s.amax(-1, keepdim=True), l=l, P=P, O=P @ v, lse=mx / 8 + torch.log(l))
+
+
+def attn_bwd_ref(s, L, q, k, v, dO, clamp):
+    """fp64 attention backward from the saved log-sum-exp L [n, T, 1], as the kernels form it: Pb = exp(s / 8 - L) (clamp: min(., 1), at_p),
+    dp = dO . v, D_i = sum_j Pb dp, dS = Pb / 8 (dp - D), dQ = dS k, dK = dS^T q, dV = Pb^T dO"""
+    Pb = torch.exp(s / 8 - L)
+    if clamp:
+        Pb = Pb.clamp(max=1.0)
+    dp = dO @ v.mT
+    Dv = (Pb * dp).sum(-1, keepdim=True)
+    dS = Pb / 8 * (dp - Dv)
+    return dict(Pb=Pb, dp=dp, e_dp=1e-6 * (dO.abs() @ v.abs().mT), D=Dv, dS=dS, dQ=dS @ k, dK=dS.mT @ q, dV=Pb.mT @ dO)
+
+
+class AttnStats:
+    """what the families' preconditions need from the fp64 reference, gathered chunk by chunk"""
+
+    def __init__(self):
+        self.rows = self.peaked_rows = 0
+        self.pmax_T = self.lse_max = self.s_max = self.D8_max = self.dS_max = self.out_max = float('-inf')
+
+    def forward(self, r, T):
+        pm = r['P'].amax(-1)
+        self.rows += pm.numel()
+        self.peaked_rows += int((pm > 0.99).sum())
+        self.pmax_T = max(self.pmax_T, pm.max().item() * T)
+        self.lse_max = max(self.lse_max, r['lse'].max().item())
+        self.s_max = max(self.s_max, r['s'].max().item())
+        self.out_max = max(self.out_max, r['O'].abs().max().item())
+
+    def backward(self, b):
+        self.D8_max = max(self.D8_max, b['D'].abs().max().item() / 8)
+        self.dS_max = max(self.dS_max, b['dS'].abs().max().item())
+        self.out_max = max(self.out_max, *(b[n].abs().max().item() for n in ('dQ', 'dK', 'dV')))
+
+    def check_forward(self, kind, what):
+        if kind == 'flat':
+            assert self.pmax_T < 1.5, '%s: not flat (max P T = %.3g)' % (what, self.pmax_T)
+        if kind == 'peaked':
+            assert 2 * self.peaked_rows >= self.rows, '%s: only %d of %d rows have max P > 0.99' % (what, self.peaked_rows, self.rows)
+        if kind in ('negative', 'loss_scaled'):
+            assert self.lse_max < 0 and self.s_max < 0, '%s: max lse %.3g, max score %.3g are not negative' % (what, self.lse_max, self.s_max)
+
+    def check_backward(self, kind, what):
+        if kind == 'loss_scaled':
+            assert self.D8_max > F16_INF_AT, '%s: max |D_i| / 8 = %.4g is inside the f16 range' % (what, self.D8_max)
+            assert self.dS_max < 65504 and self.out_max < 65504, '%s: max |dS| %.4g, max |output| %.4g' % (what, self.dS_max, self.out_max)
+        if kind == 'scaled_dO':
+            assert 1e3 < self.out_max < 65504, '%s: max |gradient| %.4g' % (what, self.out_max)
+
+
+def attn_call(lib, qkv, att, lse, datt, dqkv, S, T, heads, mode):
+    ops._L(lib, qkv).call('aph_attn_test', ops.ptr(qkv), ops.ptr(att), ops.ptr(lse), ops.ptr(datt), None, ops.ptr(dqkv), S, T, heads, mode,
+                          ops._stream(qkv))
+
+
+def ratio_within(got, ref, bound):
+    """worst |got - ref| / bound (inf where got is not finite)"""
+    if not got.numel():
+        return 0.0
+    return ((got.double() - ref).abs() / bound).nan_to_num(float('inf')).max().item()
+
+
+def ratio_f16(got, ref, e):
+    """worst err / (e + 2^-11 |ref| + 2^-25) over the elements assert_f16 bounds (those that cannot round to infinity)"""
+    e = e.expand_as(ref)
+    fin = ref.abs() + e < F16_INF_AT
+    return ratio_within(got[fin], ref[fin], (e + H * ref.abs() + H_SUB)[fin])
+
+
+class Findings:
+    """runs every assertion of a check, keeps the worst err / bound per output, and fails at the end with all of them in the message"""
+
+    def __init__(self, what):
+        self.what, self.ratio, self.failed = what, {}, []
+
+    def run(self, f, *a):
+        try:
+            f(*a)
+        except AssertionError as e:
+            self.failed.append(str(e))
+
+    def f16(self, name, got, ref, e):
+        self.ratio[name] = max(self.ratio.get(name, 0.0), ratio_f16(got, ref, e))
+        self.run(assert_f16, got, ref, e, '%s (%s)' % (self.what, name))
+
+    def within(self, name, got, ref, bound):
+        self.ratio[name] = max(self.ratio.get(name, 0.0), ratio_within(got, ref, bound))
+        self.run(assert_within, got, ref, bound, '%s (%s)' % (self.what, name))
+
+    def check(self, ok, msg):
+        if not ok:
+            self.failed.append(msg)
+
+    def finish(self):
+        assert not self.failed, '%s: worst err / bound %s\n%s' % (self.what, ' '.join('%s %.3g' % kv for kv in self.ratio.items()), '\n'.join(self.failed))
+        return self.ratio
+
+
+def attn_fwd_bound_f16(r, v, T):
+    """(e_att, e_lse) of at_fwd_tiles / attn_fwd_mfma_g_kernel; docstring of check_attention_fp64"""
+    e_x = KSL * (r['e_s'] + r['e_mx']) + 3 * U * KSL * (r['s'].abs() + r['mx'].abs())
+    eps_p = LN2 * e_x + 2 * U
+    eps_l = (r['P'] * eps_p).sum(-1, keepdim=True) + T * U
+    av = v.abs()
+    e_att = (r['P'] * (eps_p + H)) @ av + (H_SUB / r['l']) * av.sum(-2, keepdim=True) + (eps_l + (3 + T) * U) * (r['P'] @ av)
+    e_lse = r['e_mx'] / 8 + eps_l + 4 * U * (r['mx'].abs() / 8 + torch.log(r['l'])) + 2 * U
+    return e_att, e_lse
+
+
+def attn_bwd_bound_f16(r, b, L, q, k, dO, T, O16=None, eps_extra=None, eD_extra=None):
+    """(e_dQ, e_dK, e_dV) of attn_bwd_mfma_kernel (T <= 64) / attn_bwd_one_g_kernel (O16 = the f16 att rows it reads); eps_extra, eD_extra:
+    what a kernel-made lse / att adds (the chained run); docstring of check_attention_fp64"""
+    e_xb = KSL * r['e_s'] + 4 * U * (r['s'].abs() * KSL + L.abs() * LOG2E)
+    eps_pb = LN2 * e_xb + 2 * U
+    if eps_extra is not None:
+        eps_pb = eps_pb + eps_extra
+    Pb, dp, dS = b['Pb'], b['dp'], b['dS']
+    if O16 is None:
+        e_D = (Pb * (eps_pb * dp.abs() + b['e_dp'])).sum(-1, keepdim=True) + T * U * (Pb * dp.abs()).sum(-1, keepdim=True)
+    else:
+        e_D = ((O16 * dO).sum(-1, keepdim=True) - b['D']).abs() + 64 * U * (O16 * dO).abs().sum(-1, keepdim=True)
+    if eD_extra is not None:
+        e_D = e_D + eD_extra
+    e_dS = dS.abs() * (eps_pb + 3 * U) + Pb / 8 * (b['e_dp'] + e_D) + H * dS.abs() + H_SUB
+    e_dQ = e_dS @ k.abs() + 1e-6 * (dS.abs() @ k.abs())
+    e_dK = e_dS.mT @ q.abs() + 1e-6 * (dS.abs().mT @ q.abs())
+    e_dV = (Pb * (eps_pb + H) + H_SUB).mT @ dO.abs() + 1e-6 * (Pb.mT @ dO.abs())
+    return e_dQ, e_dK, e_dV
+
+
+def check_attention_fp64(lib, dev, S, T, heads, kind='normal', seed=0):
+    """The f16 attention kernels of vit_attn.h through aph_attn_test against fp64 on the f16-rounded inputs, element by element, per (cut, head):
+    the forward, the backward ALONE (fed att = f16(O_ref) and lse = f32(lse_ref), so that no forward error can cancel one of its own) and one
+    chained run (kernel forward -> kernel backward).  Outputs start as sentinels with GUARD_ROWS rows / floats behind them that must keep
+    them; inputs stay bit for bit; a second identical call gives the same bits.  At T <= 64 the backward's att input is all NaN: the
+    one-tile kernel must not read it.  Returns the worst err / bound per output ('dq+' ...: the chained run).
+
+    Notation: s = q . k raw, mx = max_j s, l = sum_j exp((s - mx) / 8), P = softmax(s / 8), U = 2^-24, H = 2^-11, H_SUB = 2^-25,
+    kSL = 0.125 log2 e, e_s = 1e-6 |q| . |k| (an fp32 MFMA accumulator, the figure of check_gemm_epilogue).
+
+    Forward (at_fwd_tiles, attn_fwd_mfma_g_kernel: the same arithmetic per score).
+      e_x   = kSL (e_s + max_j e_s) + 3 U kSL (|s| + |mx|)    the exponent fma(s, kSL, -mxs), mxs = mx * kSL: s and the maximum (a computed
+              score) carry their accumulator error; kSL is a rounded constant in both products, mxs is rounded once, the fma once
+      eps_p = ln2 e_x + 2 U                                   relative error of p = 2^x; v_exp_f32 is 1 ulp (libm's exp2f in the interpreter is less)
+      eps_l = sum_j P eps_p + T U                             l is summed from the fp32 p: at most T - 1 inexact additions (lane-local, two shuffles)
+      e_att = (P (eps_p + H)) @ |v|                           each p, then its conversion to f16 in pack8 (unnormalised: p <= 1, relative H) ...
+            + (H_SUB / l) sum_j |v_j|                         ... or absolute H_SUB where p is subnormal in f16, scaled by 1 / l like every term
+            + (eps_l + (3 + T) U) (P @ |v|)                   l itself; 1.0f / l, its shuffle-free product with o (2 U, one to spare) and the T
+                                                              accumulator additions of the two (2 NB) MFMAs at their worst case
+      e_lse = max_j e_s / 8 + eps_l + 4 U (|mx| / 8 + log l) + 2 U     mx * 0.125f is exact; __logf(l) = v_log_f32(l) * ln2: 1 ulp, a rounded
+              constant and a product (3 U log l, and an absolute 2 U where log l is near 0), the sum one rounding of |lse| <= |mx| / 8 + log l
+    Backward, alone.  L = the lse it is fed, Pb = min(exp(s / 8 - L), 1) (at_p), dp = dO . v, e_dp = 1e-6 |dO| . |v|.
+      e_xb  = kSL e_s + 4 U (|s| kSL + |L| log2 e)            fma(s, kSL, -L2), L2 = L * kLog2e: two rounded constants, the product L2, the fma
+      eps_pb = ln2 e_xb + 2 U
+      T <= 64 (attn_bwd_mfma_kernel: D_i = sum_j p dp in fp32, 16 per lane + two shuffles):
+        e_D = sum_j Pb (eps_pb |dp| + e_dp) + T U sum_j Pb |dp|
+      T > 64 (attn_bwd_one_g_kernel: D_i = dO_i . att_i from the f16 att rows, 16 products per thread + two shuffles):
+        e_D = |sum_d f16(O) dO - sum_j Pb dp| + 64 U sum_d |f16(O) dO|        the first term is the kernel's method, not its rounding: att has
+              been rounded to f16 before the kernel sees it.  Under loss_scaled (|O| ~ 16, |dO| = 640) it is as large as dp - D itself:
+              the bound on dq / dk is then wide, and that width is the blocked kernel's real precision in that regime
+      dS = Pb / 8 (dp - D) (at_ds):  e_dS = |dS| (eps_pb + 3 U) + Pb / 8 (e_dp + e_D) + H |dS| + H_SUB      p, three fp32 roundings, the
+              two inputs of the difference, the f16 fragment (pack8; the dS^T image of the blocked kernel holds the same f16 values).
+              at_ds clamps at +-65504: no valid dS of these inputs is that large (asserted for loss_scaled), so the clamp acts on padded
+              keys / queries only, whose operand rows are zero
+      e_dQ  = e_dS @ |k| + 1e-6 (|dS| @ |k|)      e_dK likewise over the queries with |q|
+      e_dV  = (Pb (eps_pb + H) + H_SUB)^T @ |dO| + 1e-6 (Pb^T @ |dO|)                                     p as an f16 fragment, as in the forward
+    Chained: the same with what the forward may hand over: eps_pb += e_lse (an error of L is a relative error of p), and at T > 64
+      e_D += |dO| . (e_att + H |O| + H_SUB) (the kernel's att rows against O).
+
+    T = 1 is exempt from any lower limit on the ratios (P = 1, dq = dk = 0)."""
+    D, M, NL, G = heads * 64, S * T, S * heads * T, GUARD_ROWS
+    what = 'attention %s S=%d T=%d heads=%d' % (kind, S, T, heads)
+    qkv, datt = attn_inputs(kind, S, T, heads, seed)
+    q, k, v = attn_items(qkv, S, T, heads, 3)
+    dO, = attn_items(datt, S, T, heads)
+    n_items = S * heads
+    step = max(1, ATTN_CHUNK // (T * T))
+    chunks = [slice(a, min(a + step, n_items)) for a in range(0, n_items, step)]
+
+    # ---- the forward reference (O and lse are the inputs of the backward alone)
+    st = AttnStats()
+    O, e_att = torch.empty_like(q), torch.empty_like(q)
+    lse, e_lse = torch.empty(n_items, T, 1, dtype=torch.float64), torch.empty(n_items, T, 1, dtype=torch.float64)
+    for c in chunks:
+        r = attn_fwd_ref(q[c], k[c], v[c])
+        st.forward(r, T)
+        O[c], lse[c] = r['O'], r['lse']
+        e_att[c], e_lse[c] = attn_fwd_bound_f16(r, v[c], T)
+    st.check_forward(kind, what)
+    O_rows = attn_rows(O, S, T, heads)
+
+    # ---- the kernels
+    ins = dict(qkv=qkv, datt=datt)
+    dd = {n: t.clone().to(dev) for n, t in ins.items()}      # (a copy: .to() of a CPU tensor aliases it)
+    held = {}
+
+    def fwd():
+        att, ls = sentinel(M + G, D, torch.float16, dev), sentinel(1, NL + G, torch.float32, dev)
+        attn_call(lib, dd['qkv'], att, ls, None, None, S, T, heads, 0)
+        held['att'], held['lse'] = att, ls
+        return att.cpu(), ls.cpu()
+
+    att_in = sentinel(M + G, D, torch.float16, 'cpu')
+    if T > 64:
+        att_in[:M] = O_rows.half()
+    lse_in = sentinel(1, NL + G, torch.float32, 'cpu')
+    lse_in[0, :NL] = lse.reshape(-1).float()
+
+    def bwd(a, ls):
+        a0, l0 = bits(a).clone(), bits(ls).clone()
+        dq = sentinel(M + G, 3 * D, torch.float16, dev)
+        attn_call(lib, dd['qkv'], a, ls, dd['datt'], dq, S, T, heads, 1)
+        assert torch.equal(bits(a), a0) and torch.equal(bits(ls), l0), what + ': the backward changed att / lse'
+        return (dq.cpu(),)
+    att, ls = _twice(fwd, what + ' forward')
+    g_alone, = _twice(lambda: bwd(att_in.clone().to(dev), lse_in.clone().to(dev)), what + ' backward')
+    g_chain, = bwd(held['att'], held['lse'])
+    _unchanged(dd, ins, what)
+
+    # ---- forward
+    fd = Findings(what)
+    fd.f16('att', att[:M], O_rows, attn_rows(e_att, S, T, heads))
+    fd.within('lse', ls[0, :NL], lse.reshape(-1), e_lse.reshape(-1))
+    fd.run(assert_untouched, att, _window(M + G, D, slice(0, M)), what + ' (att)')
+    fd.run(assert_untouched, ls, _window(1, NL + G, (0, slice(0, NL))), what + ' (lse)')
+    # ---- backward, chunk by chunk
+    L_in = lse_in[0, :NL].double().reshape(n_items, T, 1)
+    O16 = attn_items(att_in[:M], S, T, heads)[0] if T > 64 else None
+    got = {'': attn_items(g_alone[:M], S, T, heads, 3), '+': attn_items(g_chain[:M], S, T, heads, 3)}
+    for c in chunks:
+        r = attn_fwd_ref(q[c], k[c], v[c])
+        for tag in ('', '+'):
+            L = L_in[c] if tag == '' else r['lse']
+            b = attn_bwd_ref(r['s'], L, q[c], k[c], v[c], dO[c], clamp=True)
+            if tag == '':
+                st.backward(b)
+                e = attn_bwd_bound_f16(r, b, L, q[c], k[c], dO[c], T, None if O16 is None else O16[c])
+            else:
+                eD = (dO[c].abs() * (e_att[c] + H * O[c].abs() + H_SUB)).sum(-1, keepdim=True) if T > 64 else None
+                e = attn_bwd_bound_f16(r, b, L, q[c], k[c], dO[c], T, None if O16 is None else O16[c], eps_extra=e_lse[c], eD_extra=eD)
+            for i, n in enumerate(('dQ', 'dK', 'dV')):
+                fd.f16(n.lower() + tag, got[tag][i][c], b[n], e[i])
+    st.check_backward(kind, what)
+    for tag, gq in (('', g_alone), ('+', g_chain)):
+        fd.run(assert_untouched, gq, _window(M + G, 3 * D, slice(0, M)), what + ' (dqkv%s)' % tag)
+        if kind == 'loss_scaled':
+            nf = int((~torch.isfinite(gq[:M].float())).sum())
+            fd.check(nf == 0, '%s: %d NaN / inf in dqkv%s' % (what, nf, tag))
+    return fd.finish()

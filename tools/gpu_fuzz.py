@@ -5,6 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, torch
 import kernel_checks as K
+import vit_component_checks as V
 from aphantasia_amd import transforms
 transforms._EXACT_ZERO_ROT = True
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
@@ -28,7 +29,9 @@ for s in range(3):
     attempt('sampler', K.check_sampler_fuzz, None, 'cuda', seed * 100 + s, 40)
 attempt('sampler-large', K.check_sampler_fuzz, None, 'cuda', seed * 100 + 50, 16, max_hw=(500, 900))
 for it in range(20):
-    attempt('attention', K.check_attention, None, 'cuda', S=int(rng.integers(1, 40)), T=int(rng.integers(1, 257)), heads=int(rng.integers(1, 13)), seed=it)
+    shape = dict(S=int(rng.integers(1, 40)), T=int(rng.integers(1, 257)), heads=int(rng.integers(1, 13)), seed=it)
+    attempt('attention', K.check_attention, None, 'cuda', **shape)
+    attempt('attention-fp64', V.check_attention_fp64, None, 'cuda', kind=V.ATTN_KINDS[it % len(V.ATTN_KINDS)], **shape)
 for it in range(40):
     M = int(rng.integers(1, 12000)); N = 128 * int(rng.integers(1, 25)); Kk = 64 * int(rng.integers(1, 49))
     cfg = int(rng.choice([0, 1, 2, 5, 8, 9, 10, 11, 12, 22, 24]))
