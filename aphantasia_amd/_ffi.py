@@ -39,6 +39,8 @@ _PROTOTYPES = {
     'aph_synth_spatial_bwd': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_float, POINTER(c_float), c_int, c_void_p, c_void_p]),
     'aph_synth_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
     'aph_synth_set_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'aph_synth_plan_describe': (c_int, [c_void_p, POINTER(c_int)]),
+    'aph_idwt_coarse_levels': (c_int, [POINTER(c_int), POINTER(c_int), c_int, c_int]),
     'aph_rgb_priors_ws_bytes': (c_size_t, []),
     'aph_rgb_sharp': (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aph_rgb_priors': (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

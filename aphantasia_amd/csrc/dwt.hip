@@ -679,4 +679,12 @@ int aph_idwt_bwd(const float* d_img_grad, const int* hs, const int* ws, const fl
   APH_CATCH
 }
 
+// test hook (aphantasia_hip_test.h): how many levels, counted from the coarsest, aph_idwt_fwd / aph_idwt_bwd hand to the coarse-tail kernels
+int aph_idwt_coarse_levels(const int* hs, const int* ws, int J, int L) {
+  APH_TRY
+  if (const int rc = idwt_check_levels("aph_idwt_coarse_levels", hs, ws, J, 1, L)) return rc;
+  return idwt_coarse_count(hs, ws, J, L);
+  APH_CATCH
+}
+
 }  // extern "C"

@@ -658,6 +658,21 @@ int aph_synth_plan_destroy(aph_synth_plan* p) {
   return APH_OK;
 }
 
+// test hook (aphantasia_hip_test.h): the plan's column tile and the radices of both transforms, in pass order
+int aph_synth_plan_describe(const aph_synth_plan* p, int* out31) {
+  APH_TRY
+  if (!p || !out31) return aph_fail(APH_ERR_ARG, "aph_synth_plan_describe: null argument");
+  out31[0] = p->TC;
+  const Fft1D* plans[2] = {&p->ph, &p->pw};
+  for (int a = 0; a < 2; ++a) {
+    int* o = out31 + 1 + 15 * a;
+    o[0] = plans[a]->npass;
+    for (int i = 0; i < 14; ++i) o[1 + i] = i < plans[a]->npass ? plans[a]->radix[i] : 0;
+  }
+  return APH_OK;
+  APH_CATCH
+}
+
 static ColorMat to_cm(const float* cc) { ColorMat m; for (int i = 0; i < 9; ++i) m.m[i] = cc ? cc[i] : (i % 4 == 0 ? 1.f : 0.f); return m; }
 
 // params [C,H,Wc,2] f32, scale [H,Wc] f32, shift [H,Wc] f32 or NULL  ->  raw [C,H,W], rgb [C,H,W]

@@ -89,6 +89,15 @@ int aph_ln_test(int mode, int D, int M, int T, int xs, int res_T, int flags, con
                 const void* d_res, void* d_out, void* d_out2, const float* d_cls, const float* d_pos, float* d_x_fill, const float* d_x2,
                 const float* d_g2, const float* d_b2, void* stream);
 
+/* Read-only descriptions of the path a parameteriser call takes (tests/param_checks.py asserts them per case, so that a retuned tile
+ * constant cannot silently move a case onto another kernel).
+ *   aph_idwt_coarse_levels: the number of levels, counted from the coarsest, that aph_idwt_fwd / aph_idwt_bwd run in the single coarse-tail
+ *     launch (0: one launch per level).  hs / ws / J / L as for aph_idwt_fwd (host arrays, level 0 = finest).
+ *   aph_synth_plan_describe: out31[0] = columns per workgroup of the column pass (TC); out31[1] = number of passes over H and
+ *     out31[2 .. 15] their radices in order (0 beyond the last pass); out31[16], out31[17 .. 30] the same for W. */
+int aph_idwt_coarse_levels(const int* hs, const int* ws, int J, int L);
+int aph_synth_plan_describe(const aph_synth_plan* plan, int* out31);
+
 /* Crop / resize adjoint of aph_sample_bwd: 1 = always the per-pixel gather kernel (round 2), 0 = automatic (the separable row-block kernel
  * on frames without wrap padding).  Process-wide, returns the previous value.  (No environment variable changes which kernels the library
  * runs: every switch here is an explicit call.) */

@@ -56,7 +56,10 @@ def dwt_scale(Ys, sharp):
     return [((h0 * w0) / (Ys[i + 1].shape[3] * Ys[i + 1].shape[4])) ** (1. - sharp) for i in range(len(Ys) - 1)]
 
 
-def sfb1d(lo, hi, g0, g1, dim):
+def sfb1d(lo, hi, g0, g1, dim, absolute=False):
+    """absolute: with |rec_lo| and |rec_hi| -- on |inputs| the sum of the magnitudes of every term, the scale of a rounding-error bound"""
+    if absolute:
+        g0, g1 = g0.abs(), g1.abs()
     C = lo.shape[1]
     L = g0.numel()
     shape = [1, 1, 1, 1]
@@ -68,7 +71,7 @@ def sfb1d(lo, hi, g0, g1, dim):
     return F.conv_transpose2d(lo, k0, stride=s, padding=pad, groups=C) + F.conv_transpose2d(hi, k1, stride=s, padding=pad, groups=C)
 
 
-def idwt(yl, yh, wave):
+def idwt(yl, yh, wave, absolute=False):
     """DWTInverse(wave, 'symmetric')((yl, yh)), yh finest first"""
     g0, g1 = filters(wave)
     ll = yl
@@ -78,16 +81,16 @@ def idwt(yl, yh, wave):
         if ll.shape[-1] > h.shape[-1]:
             ll = ll[..., :-1]
         lh, hl, hh = torch.unbind(h, dim=2)
-        lo = sfb1d(ll, lh, g0, g1, 2)
-        hi = sfb1d(hl, hh, g0, g1, 2)
-        ll = sfb1d(lo, hi, g0, g1, 3)
+        lo = sfb1d(ll, lh, g0, g1, 2, absolute)
+        hi = sfb1d(hl, hh, g0, g1, 2, absolute)
+        ll = sfb1d(lo, hi, g0, g1, 3, absolute)
     return ll
 
 
-def dwt_image_raw(Ys, wave, sharp=0.3):
+def dwt_image_raw(Ys, wave, sharp=0.3, absolute=False):
     """image.py:67: ifm((Ys[0], [Ys[i+1] * scale[i]]))"""
     scale = dwt_scale(Ys, sharp)
-    return idwt(Ys[0], [Ys[i + 1] * float(scale[i]) for i in range(len(Ys) - 1)], wave)
+    return idwt(Ys[0], [Ys[i + 1] * float(scale[i]) for i in range(len(Ys) - 1)], wave, absolute)
 
 
 def synth_dwt(Ys, wave, cc_t, sharp=0.3, contrast=1.0):

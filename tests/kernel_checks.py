@@ -604,6 +604,32 @@ def check_adam_guard(lib, dev):
         pc, vc = run(gb, True)
         assert torch.equal(pc, p0) and torch.equal(vc, v0)
     assert guard.cpu().tolist()[0] == 3
+    # where the scan can lose an element: the scalar tail behind the 16-byte quads (n = 5003, index 5002), the last element of a buffer
+    # longer than one grid pass of the scan (2048 workgroups x 256 quads < 2769120 / 4: the grid-stride loop), index 0, and buffers that
+    # start one float into their allocation (not 16-byte aligned: the scalar scan).  Each: a finite gradient updates exactly as
+    # aph_adam_step, the bad one leaves every buffer as it was and counts one skipped step.
+    def off(t, offset):
+        big = torch.zeros(t.numel() + offset, device=dev)
+        big[offset:] = t.to(dev)
+        return big[offset:]
+    for (n2, idx, offset) in ((5003, 5002, 0), (2769120, 2769119, 0), (5003, 0, 0), (5003, 5002, 1)):
+        p1 = torch.randn(n2, generator=g); g1 = torch.randn(n2, generator=g); v1 = torch.rand(n2, generator=g)
+        guard2 = torch.zeros(2, dtype=torch.int32, device=dev)
+        def run2(gr, guarded):
+            p, v, gr = off(p1, offset), off(v1, offset), off(gr, offset)
+            assert p.data_ptr() % 16 == (4 * offset) % 16
+            if guarded:
+                L.call('aph_adam_step_guarded', ops.ptr(p), ops.ptr(gr), None, ops.ptr(v), None, ops.ptr(hyper), 0, n2, ops.ptr(guard2), ops._stream(p))
+            else:
+                L.call('aph_adam_step', ops.ptr(p), ops.ptr(gr), None, ops.ptr(v), None, ops.ptr(hyper), 0, n2, ops._stream(p))
+            return p.cpu(), v.cpu()
+        pa, va = run2(g1, False)
+        pb, vb = run2(g1, True)
+        assert torch.equal(pa, pb) and torch.equal(va, vb) and not torch.equal(pa, p1) and guard2.cpu().tolist()[0] == 0, (n2, idx, offset)
+        for k, bad in enumerate((float('nan'), float('inf'), -float('inf'))):
+            gb = g1.clone(); gb[idx] = bad
+            pc, vc = run2(gb, True)
+            assert torch.equal(pc, p1) and torch.equal(vc, v1) and guard2.cpu().tolist()[0] == k + 1, (n2, idx, offset, bad)
 
 
 def check_depthwarp(lib, dev, g, sizes=((40, 56), (37, 51), (64, 48))):

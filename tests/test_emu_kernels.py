@@ -13,6 +13,7 @@ import torch
 from aphantasia_amd import _ffi
 import kernel_checks as K
 import vit_component_checks as V
+import param_checks as P
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), 'emu'))
 
@@ -316,3 +317,14 @@ def test_attention_families_vs_fp64(emu, kind, T):
 def test_attention_vs_fp64_item_loop(emu):
     """10 (cut, head) items on 3 persistent workgroups (4 / 3 / 3 items each), two heads"""
     _show('S=5 T=50 heads=2', V.check_attention_fp64(emu, 'cpu', S=5, T=50, heads=2, seed=7))
+
+
+# ---- the image parameterisers against fp64 (param_checks.py); the path each case expects is asserted through the library's description of it
+@pytest.mark.parametrize('wave,h,w,tail', P.IDWT_CASES, ids=lambda v: str(v))
+def test_idwt_vs_fp64(emu, wave, h, w, tail):
+    P.show('idwt %s %dx%d tail %d' % (wave, h, w, tail), P.check_idwt_fp64(emu, 'cpu', wave, h, w, tail=tail))
+
+
+@pytest.mark.parametrize('h,w,tc,rad_h,rad_w', [c[:5] for c in P.FFT_CASES if c[5]], ids=['%dx%d' % c[:2] for c in P.FFT_CASES if c[5]])
+def test_fft_vs_fp64(emu, h, w, tc, rad_h, rad_w):
+    P.show('fft %dx%d TC %d' % (h, w, tc), P.check_fft_fp64(emu, 'cpu', h, w, tc=tc, rad_h=rad_h, rad_w=rad_w))

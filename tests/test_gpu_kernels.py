@@ -8,6 +8,7 @@ import torch
 from aphantasia_amd import _ffi, ops
 import kernel_checks as K
 import vit_component_checks as V
+import param_checks as P
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -370,3 +371,19 @@ def test_attention_families_vs_fp64_product_shapes(kind, S, T):
     """every input family at the product's shapes: ViT-B/32 at 190 cuts (2280 items: more than the persistent backward's workgroups, the item
     loop) and ViT-B/16 at the 95 cuts of BASELINE configs[3] (400 samples x 0.25 x 0.95)"""
     _show('S=%d T=%d %s' % (S, T, kind), V.check_attention_fp64(None, DEV, S=S, T=T, heads=12, kind=kind, seed=5))
+
+
+def test_rgb_to_u8():
+    K.check_rgb_to_u8(None, DEV)
+
+
+# ---- the image parameterisers against fp64 (param_checks.py): every instantiation of the inverse DWT and every path of the FFT synthesis.
+# Each case asserts the path it expects (coarse-tail levels; column tile, radices) through the library's own description of it.
+@pytest.mark.parametrize('wave,h,w,tail', P.IDWT_CASES + P.IDWT_CASES_PRODUCT, ids=lambda v: str(v))
+def test_idwt_vs_fp64(wave, h, w, tail):
+    P.show('idwt %s %dx%d tail %d' % (wave, h, w, tail), P.check_idwt_fp64(None, DEV, wave, h, w, tail=tail))
+
+
+@pytest.mark.parametrize('h,w,tc,rad_h,rad_w', [c[:5] for c in P.FFT_CASES], ids=['%dx%d' % c[:2] for c in P.FFT_CASES])
+def test_fft_vs_fp64(h, w, tc, rad_h, rad_w):
+    P.show('fft %dx%d TC %d' % (h, w, tc), P.check_fft_fp64(None, DEV, h, w, tc=tc, rad_h=rad_h, rad_w=rad_w))
