@@ -169,28 +169,28 @@ def test_skip_count_bookkeeping_across_reset_params():
     # (1) one skip in frame A, then the reset: the new frame's optimiser must not pay for it
     eng.guard[0] = 1
     eng.reset_params(p0)
-    assert eng._state['step'][0] == 0 and eng._guard_floor == 1
+    assert eng._state['step'][0] == 0 and eng._guard.floor == 1
     eng._state['step'][0] = 3                     # three steps of frame B taken
     look()
-    assert eng._state['step'][0] == 3 and eng._guard_seen == 1
-    assert eng.loss_scale == scale0 * 0.5 and eng._graphs is None       # (the overflow is still answered with a smaller loss scale)
+    assert eng._state['step'][0] == 3 and eng._guard.seen == 1
+    assert eng.loss_scale == scale0 * 0.5 and eng._graph is None       # (the overflow is still answered with a smaller loss scale)
     # (2) a genuine skip of frame B right after the reset IS charged
     eng.guard[0] = 2
     look(2)
-    assert eng._state['step'][0] == 2 and eng._guard_seen == 2
+    assert eng._state['step'][0] == 2 and eng._guard.seen == 2
     # (3) two resets inside one window: skip in frame B (counter 3), reset -> frame C, skip in frame C (counter 4), reset -> frame D
     eng.guard[0] = 3
     eng.reset_params(p0)
     eng.guard[0] = 4
     eng.reset_params(p0)
-    assert eng._guard_floor == 4
+    assert eng._guard.floor == 4
     eng._state['step'][0] = 5
     look(3)
-    assert eng._state['step'][0] == 5 and eng._guard_seen == 4          # neither skip belongs to frame D
+    assert eng._state['step'][0] == 5 and eng._guard.seen == 4          # neither skip belongs to frame D
     # (4) keep_optimizer_state (--smooth) keeps the step counter and the floor where they are
     eng.guard[0] = 5
     eng.reset_params(p0, keep_optimizer_state=True)
-    assert eng._guard_floor == 4 and eng._state['step'][0] == 5
+    assert eng._guard.floor == 4 and eng._state['step'][0] == 5
     look(4)
     assert eng._state['step'][0] == 4
     # the step counter never goes below zero
@@ -198,3 +198,39 @@ def test_skip_count_bookkeeping_across_reset_params():
     eng.guard[0] = 9
     look(5)
     assert eng._state['step'][0] == 0
+
+
+def test_step_inputs_layout_and_cpu_upload():
+    """StepInputs, fullest layout (Adam scalars, crop + augment table, the second set of --enforce) at 5 cuts: the named views have the
+    stated shapes and dtypes, start on 16-byte boundaries of the one flat buffer and do not overlap (the 15-word crop tables need a
+    word of padding), and a CPU upload writes the words of the item it was given and no others"""
+    from aphantasia_amd.engine import StepInputs, step_input_parts
+    Sl, A = 5, _ffi.APH_AUG_STRIDE
+    want = [('hyper', (8,), torch.float32), ('table', (Sl, 3), torch.int32), ('aug', (Sl, A), torch.float32),
+            ('table2', (Sl, 3), torch.int32), ('aug2', (Sl, A), torch.float32)]
+    si = StepInputs(step_input_parts(Sl, True, True), torch.device('cpu'))
+    assert si.flat.dtype == torch.int32 and si.flat.dim() == 1 and list(si.views) == [name for name, _, _ in want]
+    base, spans = si.flat.data_ptr(), {}
+    for name, shape, dt in want:
+        v = si.views[name]
+        assert tuple(v.shape) == shape and v.dtype == dt and v.is_contiguous(), name
+        off = v.data_ptr() - base
+        assert off % 16 == 0 and 0 <= off and off + 4 * v.numel() <= 4 * si.flat.numel(), (name, off)
+        spans[name] = (off // 4, off // 4 + v.numel())
+    order = sorted(spans.values())
+    assert all(a[1] <= b[0] for a, b in zip(order, order[1:]))           # disjoint
+    g = torch.Generator().manual_seed(7)
+    for name, shape, dt in want:                                         # one item at a time: its view takes it, every other word stays
+        src = torch.randint(1, 1000, shape, generator=g).to(dt)
+        before = si.flat.clone()
+        si.upload([(name, src)])
+        assert torch.equal(si.views[name], src), name
+        lo, hi = spans[name]
+        assert torch.equal(si.flat[:lo], before[:lo]) and torch.equal(si.flat[hi:], before[hi:]), name
+    vals = [(name, torch.randint(1, 1000, shape, generator=g).to(dt)) for name, shape, dt in want]
+    si.upload(vals)                                                      # and all of them in one call, as a step does
+    for name, src in vals:
+        assert torch.equal(si.views[name], src), name
+    plain = StepInputs(step_input_parts(Sl, False, False), torch.device('cpu'))      # the smallest layout has no other views
+    assert list(plain.views) == ['hyper', 'table']
+

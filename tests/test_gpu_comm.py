@@ -64,7 +64,7 @@ def test_step_with_in_graph_allreduce_matches_plain_step():
     b = run(c, False)
     d = run(c, True)
     # the capture self-check (one eager step against one replay from the same state, agreed through the communicator) ran and passed
-    assert run.last._graph_checked and run.last.use_graph and run.last._graphs is not None
+    assert run.last._graph_checked and run.last.use_graph and run.last._graph is not None
     for x, y in ((a, b), (a, d)):
         assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) and x[2] == y[2]
     assert torch.isfinite(a[0]).all()
@@ -75,7 +75,7 @@ def test_step_with_in_graph_allreduce_matches_plain_step():
         e = run(c, True)
     finally:
         Engine._same_bits = saved
-    assert run.last._graph_checked and not run.last.use_graph and run.last._graphs is None
+    assert run.last._graph_checked and not run.last.use_graph and run.last._graph is None
     assert torch.equal(a[0], e[0]) and torch.equal(a[1], e[1]) and a[2] == e[2]
 
 
@@ -104,7 +104,7 @@ def _rank_main(rank, world, port, ret, same_device=False, graph_allreduce=False)
         eng.step()
         losses.append(eng.global_loss())
     torch.cuda.synchronize()
-    ret[rank] = (eng.params.cpu(), losses, bool(eng.use_graph and eng._graphs is not None))
+    ret[rank] = (eng.params.cpu(), losses, bool(eng.use_graph and eng._graph is not None))
 
 
 def _two_ranks(same_device, graph_allreduce, port, timeout=600):

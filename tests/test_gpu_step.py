@@ -458,6 +458,36 @@ def test_loss_scale_backs_off_after_fp16_overflow(model):
     assert last < first - 0.02, (first, last, eng.loss_scale)
 
 
+def test_guard_polls_and_reset_between_graph_replays_match_eager(model):
+    """One run that crosses everything the step's host side does around the launches: two eager steps, the capture, replays, a look at
+    the skipped-step counter every second step and a reset_params (same parameters, fresh optimiser) after step 5 with replays after
+    it -- 8 seeded steps, hipGraph engine == eager engine bit for bit, no step skipped, the graph still held at the end"""
+    from aphantasia_amd.engine import Engine
+    from aphantasia_amd import transforms
+    h, w, S = 256, 320, 6
+    target = torch.randn(1, 512, generator=torch.Generator().manual_seed(2))
+
+    def run(graph):
+        seed_all(0)
+        params = (0.01 * torch.randn(1, 3, h, w // 2 + 1, 2)).to(DEV).contiguous()
+        eng = Engine(params, h, w, model, S, [(target, -1.0)], sim='mix', transform=transforms.transforms_fast, macro=0.4, rng='reference',
+                     use_graph=graph)
+        eng.GUARD_EVERY = 2
+        for i in range(8):
+            seed_all(100 + i)
+            eng.step()
+            if i == 4:
+                eng.reset_params(eng.params.detach().clone())
+        torch.cuda.synchronize()
+        return eng
+    a, b = run(False), run(True)
+    assert a._graph is None and b.use_graph and b._graph is not None
+    assert torch.equal(a.params, b.params) and torch.equal(a.grad, b.grad)
+    assert a.step_count == b.step_count == 3
+    assert float(a.loss) == float(b.loss) and np.isfinite(float(a.loss))
+    assert int(a.guard[0]) == 0 and int(b.guard[0]) == 0
+
+
 @pytest.mark.parametrize('gen', ['RGB', 'FFT'])
 def test_illustrip_cli_frames_with_and_without_depth(tmp_path, monkeypatch, gen):
     """illustrip.py end to end (synthetic CLIP weights): frames on disk, no skipped steps; `-d` runs the depth warp with a stand-in

@@ -34,5 +34,5 @@ for i in range(12):
         if 'sleep' in mode:
             import time; time.sleep(0.5)
     losses.append(float(eng.loss) if 'noread' not in mode or i == 11 else 0.0)
-print(mode, 'losses', ['%.5f' % v for v in losses], 'graph captured:', eng._graphs is not None, 'nan:', bool(torch.isnan(eng.params).any()))
+print(mode, 'losses', ['%.5f' % v for v in losses], 'graph captured:', eng._graph is not None, 'nan:', bool(torch.isnan(eng.params).any()))
 dist.destroy_process_group()
