@@ -164,7 +164,7 @@ def sample_fwd(geom, rgb, table, aug=None, tmp=None, out=None, out_mode=_ffi.APH
 
 def sample_bwd(geom, gout, table, aug=None, tmp=None, out=None, out_mode=_ffi.APH_OUT_NCHW_NORM, gscale=1.0, lib=None):
     L = _L(lib, gout, table, aug)
-    _chk(gout, torch.float32, 'gout')
+    _chk(gout, torch.float16 if out_mode == _ffi.APH_GRAD_PATCH_F16 else torch.float32, 'gout')
     if out is None:
         out = torch.empty(3, geom.H, geom.W, dtype=torch.float32, device=gout.device)
     if tmp is None:

@@ -180,7 +180,7 @@ def check_sampler_augment(lib, dev, H=40, W=48, S=6, size=16, patch=8):
     tb = torch.from_numpy(table).to(dev)
     out = ops.sample_fwd(geom, img.detach()[0].to(dev).contiguous(), tb, aug=aug, lib=lib)
     assert (out.cpu() - cuts.detach()).abs().max().item() < 3e-4
-    # the patch-major f16 emit (LDS-staged 16-byte stores for full tiles) holds the same values
+    # the patch-major f16 emit (rotate_emit_kernel writes each pixel's three channels straight into its patch row) holds the same values
     pm = ops.sample_fwd(geom, img.detach()[0].to(dev).contiguous(), tb, aug=aug, out_mode=_ffi.APH_OUT_PATCH_F16, lib=lib)
     assert torch.equal(pm.cpu(), to_patch_major(out.cpu(), patch).half())
     # the split-precision rows [hi | lo] (APH_OUT_PATCH_F16_HILO): hi = the plain f16 emit, hi + lo = the f32 value to ~2^-22; with and without -tf fast
@@ -192,6 +192,68 @@ def check_sampler_augment(lib, dev, H=40, W=48, S=6, size=16, patch=8):
         assert (hl[:, :kp].float() + hl[:, kp:].float() - f32).abs().max().item() < 2e-6 * max(f32.abs().max().item(), 1.0)
     got = ops.sample_bwd(geom, gout.to(dev).contiguous(), tb, aug=aug, lib=lib)
     assert (got.cpu() - img.grad[0]).abs().max().item() < 3e-4 * img.grad.abs().max().item()
+
+
+CROP_ADJOINT_GEOMS = ((40, 56, 5, 16, 8), (40, 56, 30, 16, 8), (23, 37, 14, 8, 4))       # (H, W, S, size, patch)
+# (rb, cpt, nbc, nseg, order) for aph_crop_adjoint_set_shape; the first is the automatic shape
+CROP_ADJOINT_SHAPES = ((0, 0, 0, 0, -1), (4, 2, 12, 1, 0), (16, 3, 5, 1, 1), (13, 2, 1, 2, 1), (9, 3, 12, 3, 0), (16, 2, 3, 1, 1))
+REL_ROUNDING = 2e-6       # two fp32 summation orders of the same <= 16 x S products per pixel (test_crop_adjoint_rows_kernel_vs_gather_kernel_full_size)
+
+
+def _crop_adjoint_case(dev, H, W, S, size, patch):
+    """seeded crop table (cut 0 up-sampling) and a patch-major f32 gradient for one geometry"""
+    seed_all(3)
+    table = R.draw_crop_table(S, size, H, W, 'uniform', 0.4)
+    table[0] = (size - 3, 1, 2)          # one up-sampling cut (csize < size)
+    gout = torch.randn(S, 3, size, size)
+    return ops.make_geom(H, W, S, size, patch=patch), torch.from_numpy(table).to(dev), gout
+
+
+def check_crop_adjoint_paths(lib, dev):
+    """the separable crop adjoint in all four (accumulator rows, columns per thread) instantiations, several column segments, both
+    row-block orders, one-cut batches and more than one batch of 12 cuts (double-buffered tables), ragged last row blocks and an
+    up-sampling cut, in every gradient layout: equal to the gather kernel up to summation order, and the same bits on every launch"""
+    L = lib if lib is not None else _ffi.lib()
+    for (H, W, S, size, patch) in CROP_ADJOINT_GEOMS:
+        geom, tb, gout = _crop_adjoint_case(dev, H, W, S, size, patch)
+        pm = to_patch_major(gout, patch).contiguous()
+        for mode, gin in ((_ffi.APH_OUT_NCHW_RAW, gout), (_ffi.APH_OUT_NCHW_NORM, gout), (_ffi.APH_OUT_PATCH_F16, pm), (_ffi.APH_GRAD_PATCH_F16, pm.half())):
+            gin = gin.to(dev).contiguous()
+            run = lambda: ops.sample_bwd(geom, gin, tb, out_mode=mode, gscale=0.5, lib=lib).clone()
+            prev = L.cdll.aph_crop_adjoint_set_gather(1)
+            try:
+                want = run()
+            finally:
+                L.cdll.aph_crop_adjoint_set_gather(prev)
+            try:
+                for shape in CROP_ADJOINT_SHAPES:
+                    L.call('aph_crop_adjoint_set_shape', *shape)
+                    got, again = run(), run()
+                    err = (got - want).abs().max().item() / want.abs().max().item()
+                    print('crop adjoint %dx%d S=%d mode %d shape %s: %.3g' % (H, W, S, mode, shape, err))
+                    assert err < REL_ROUNDING, (H, W, S, mode, shape, err)
+                    assert torch.equal(got, again), (H, W, S, mode, shape)
+            finally:
+                L.call('aph_crop_adjoint_set_shape', 0, 0, 0, 0, -1)
+
+
+def check_sampler_f16_gradient(lib, dev):
+    """APH_GRAD_PATCH_F16 (the f16 input gradient of the ViT) gives what APH_OUT_PATCH_F16 gives for the same values as f32, with and
+    without -tf fast.  Same sums in the same order: equal bits under the interpreter; on the GPU the two template instantiations
+    may contract their multiply-adds differently, so a rounding-level bound there (as check_dwt's per-level comparison)"""
+    for (H, W, S, size, patch) in CROP_ADJOINT_GEOMS[:2]:
+        geom, tb, gout = _crop_adjoint_case(dev, H, W, S, size, patch)
+        prm = [augment_ref.draw_fast_params(size) for _ in range(S)]
+        g16 = to_patch_major(gout, patch).half().to(dev).contiguous()
+        for aug in (None, pack_aug(prm).to(dev)):
+            got = ops.sample_bwd(geom, g16, tb, aug=aug, out_mode=_ffi.APH_GRAD_PATCH_F16, gscale=0.5, lib=lib)
+            want = ops.sample_bwd(geom, g16.float(), tb, aug=aug, out_mode=_ffi.APH_OUT_PATCH_F16, gscale=0.5, lib=lib)
+            if dev == 'cpu':
+                assert torch.equal(got, want), (H, W, S, aug is not None)
+            else:
+                err = (got - want).abs().max().item() / want.abs().max().item()
+                print('f16 gradient %dx%d S=%d aug %s: %.3g' % (H, W, S, aug is not None, err))
+                assert err < REL_ROUNDING, (H, W, S, aug is not None, err)
 
 
 TV_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tf_fast_224.npz')

@@ -75,7 +75,15 @@ def test_sampler_adjoint_column_segments(emu):
 
 def test_sampler_augment(emu):
     K.check_sampler_augment(emu, 'cpu')
-    K.check_sampler_augment(emu, 'cpu', H=80, W=96, S=6, size=64, patch=16)      # full 32x32 tiles: LDS-staged patch-major emit
+    K.check_sampler_augment(emu, 'cpu', H=80, W=96, S=6, size=64, patch=16)      # cuts of several whole 32 x 8 workgroup tiles, 4 x 4 patches of 16
+
+
+def test_crop_adjoint_paths(emu):
+    K.check_crop_adjoint_paths(emu, 'cpu')
+
+
+def test_sampler_f16_gradient(emu):
+    K.check_sampler_f16_gradient(emu, 'cpu')
 
 
 def test_augment_kernels_vs_pillow(emu):

@@ -77,6 +77,14 @@ def test_sampler_augment():
     K.check_sampler_augment(None, DEV, H=360, W=640, S=12, size=224, patch=32)
 
 
+def test_crop_adjoint_paths():
+    K.check_crop_adjoint_paths(None, DEV)
+
+
+def test_sampler_f16_gradient():
+    K.check_sampler_f16_gradient(None, DEV)
+
+
 def test_augment_invariants():
     K.check_augment_invariants(None, DEV)
     K.check_augment_invariants(None, DEV, size=224, patch=32)
