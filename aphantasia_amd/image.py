@@ -48,6 +48,24 @@ def fft_scale(h, w, decay_power):
     return torch.tensor(scale).float()
 
 
+def _read_stats(plan, raw):
+    """{mean, std} of `raw` as the plan's last forward left them: kept by the autograd node, other forwards may follow before its backward"""
+    stats = torch.empty(2, dtype=torch.float32, device=raw.device)
+    plan.lib.call('aph_synth_stats', plan.handle, ops.ptr(stats), ops._stream(raw))
+    return stats
+
+
+def _restore_stats(plan, stats, raw):
+    plan.lib.call('aph_synth_set_stats', plan.handle, ops.ptr(stats), ops._stream(raw))
+
+
+def _std_normalise_bwd(g, raw, stats, c):
+    """adjoint of x * c / std(x):  d raw = c/s g - c sum(g x) / (s^3 (N-1)) (x - mean)"""
+    n, s, mu = raw.numel(), stats[1], stats[0]
+    sgx = (g.double() * raw.double()).sum().float()
+    return (c / s) * g - (c * sgx / (s ** 3 * (n - 1))) * (raw - mu)
+
+
 class _SynthFFT(torch.autograd.Function):
     """rgb (or the normalised pre-rgb image) from the spectrum: K1-K4 fused (csrc/synth.hip)."""
 
@@ -56,43 +74,29 @@ class _SynthFFT(torch.autograd.Function):
         p = params.reshape(3, gen.h, gen.wc, 2)
         raw, out = ops.synth_fft_fwd(gen.plan, p.contiguous(), gen.scale, shift, contrast,
                                      cc if to_rgb else None, decorrelate and to_rgb)
+        stats = _read_stats(gen.plan, raw)
         if not to_rgb:
-            # image_f() without to_valid_rgb: image * contrast / std  (image.py:174)
-            stats = torch.empty(2, dtype=torch.float32, device=raw.device)
-            gen.plan.lib.call('aph_synth_stats', gen.plan.handle, ops.ptr(stats), ops._stream(raw))
-            out = raw * (contrast / stats[1])
-            ctx.plain = True
-            ctx.save_for_backward(raw, stats)
-            ctx.contrast = contrast
-            ctx.gen = gen
-            return out.unsqueeze(0)
-        stats = torch.empty(2, dtype=torch.float32, device=raw.device)
-        gen.plan.lib.call('aph_synth_stats', gen.plan.handle, ops.ptr(stats), ops._stream(raw))
-        ctx.plain = False
+            out = raw * (contrast / stats[1])      # image_f() without to_valid_rgb: image * contrast / std  (image.py:174)
+        ctx.plain = not to_rgb
         ctx.gen, ctx.contrast, ctx.cc, ctx.decorrelate = gen, contrast, cc, decorrelate
-        ctx.save_for_backward(raw, out, stats)
+        ctx.save_for_backward(*((raw, stats) if ctx.plain else (raw, out, stats)))
         return out.unsqueeze(0)
 
     @staticmethod
     def backward(ctx, g):
         gen = ctx.gen
         g = g.reshape(3, gen.h, gen.w).contiguous().float()
+        raw, *rgb, stats = ctx.saved_tensors
         if ctx.plain:
-            raw, stats = ctx.saved_tensors
-            # adjoint of x*c/std through the identity colour path: rgb' = 1 is emulated by feeding the
-            # spatial adjoint pieces directly: d raw = c/s g - c sum(g x)/(s^3 (N-1)) (x - mean)
-            n = raw.numel()
-            s, mu, c = stats[1], stats[0], ctx.contrast
-            sgx = (g.double() * raw.double()).sum().float()
-            draw = (c / s) * g - (c * sgx / (s ** 3 * (n - 1))) * (raw - mu)
-            ones = torch.full_like(raw, 0.5)      # sigmoid'(0)*4 = 1: feed rgb = 0.5 with 4x gradient, identity colour
-            gen.plan.lib.call('aph_synth_set_stats', gen.plan.handle, ops.ptr(torch.stack([mu * 0, s * 0 + 1]).contiguous()),
-                              ops._stream(raw))
+            # the normalisation's adjoint in torch, then the transform's adjoint alone: statistics {0, 1} and contrast 1 make the
+            # kernels' normalisation the identity, rgb = 0.5 with a 4x gradient their sigmoid (sigmoid'(0) * 4 = 1), identity colour
+            draw = _std_normalise_bwd(g, raw, stats, ctx.contrast)
+            ones = torch.full_like(raw, 0.5)
+            _restore_stats(gen.plan, torch.stack([stats[0] * 0, stats[1] * 0 + 1]).contiguous(), raw)
             grad = ops.synth_fft_bwd(gen.plan, (draw * 4.0).contiguous(), ones, raw * 0, gen.scale, 1.0, None, False)
-            return grad.reshape(gen.param_shape), None, None, None, None, None, None
-        raw, rgb, stats = ctx.saved_tensors
-        gen.plan.lib.call('aph_synth_set_stats', gen.plan.handle, ops.ptr(stats), ops._stream(raw))
-        grad = ops.synth_fft_bwd(gen.plan, g, rgb, raw, gen.scale, ctx.contrast, ctx.cc, ctx.decorrelate)
+        else:
+            _restore_stats(gen.plan, stats, raw)
+            grad = ops.synth_fft_bwd(gen.plan, g, rgb[0], raw, gen.scale, ctx.contrast, ctx.cc, ctx.decorrelate)
         return grad.reshape(gen.param_shape), None, None, None, None, None, None
 
 
@@ -213,8 +217,7 @@ class _SpatialRGB(torch.autograd.Function):
     def forward(ctx, image, plan, contrast, fixed_div, cc, decorrelate):
         raw = image.reshape(3, plan.H, plan.W).contiguous().float()
         rgb = ops.synth_spatial_fwd(plan, raw, contrast, fixed_div, cc, decorrelate)
-        stats = torch.empty(2, dtype=torch.float32, device=raw.device)
-        plan.lib.call('aph_synth_stats', plan.handle, ops.ptr(stats), ops._stream(raw))
+        stats = _read_stats(plan, raw)
         ctx.plan, ctx.args = plan, (contrast, fixed_div, cc, decorrelate)
         ctx.save_for_backward(raw, rgb, stats)
         ctx.shape = image.shape
@@ -225,7 +228,7 @@ class _SpatialRGB(torch.autograd.Function):
         raw, rgb, stats = ctx.saved_tensors
         plan = ctx.plan
         contrast, fixed_div, cc, decorrelate = ctx.args
-        plan.lib.call('aph_synth_set_stats', plan.handle, ops.ptr(stats), ops._stream(raw))
+        _restore_stats(plan, stats, raw)
         d = ops.synth_spatial_bwd(plan, g.reshape(3, plan.H, plan.W).contiguous().float(), rgb, raw, contrast, fixed_div, cc, decorrelate)
         return d.reshape(ctx.shape), None, None, None, None, None
 
@@ -279,8 +282,7 @@ class _SynthDWT(torch.autograd.Function):
             out = ops.synth_spatial_fwd(gen.plan, raw, contrast, 0.0, cc, decorrelate)
         else:
             out = ops.synth_spatial_fwd(gen.plan, raw, contrast, 0.0, None, False)      # still needs the std
-        stats = torch.empty(2, dtype=torch.float32, device=raw.device)
-        gen.plan.lib.call('aph_synth_stats', gen.plan.handle, ops.ptr(stats), ops._stream(raw))
+        stats = _read_stats(gen.plan, raw)
         ctx.gen, ctx.args, ctx.to_rgb = gen, (contrast, cc, decorrelate), to_rgb
         if not to_rgb:
             out = raw * (contrast / stats[1])
@@ -294,12 +296,10 @@ class _SynthDWT(torch.autograd.Function):
         contrast, cc, decorrelate = ctx.args
         g = g.reshape(raw.shape).contiguous().float()
         if ctx.to_rgb:
-            gen.plan.lib.call('aph_synth_set_stats', gen.plan.handle, ops.ptr(stats), ops._stream(raw))
+            _restore_stats(gen.plan, stats, raw)
             d_raw = ops.synth_spatial_bwd(gen.plan, g, out, raw, contrast, 0.0, cc, decorrelate)
         else:
-            n, s, mu = raw.numel(), stats[1], stats[0]
-            sgx = (g.double() * raw.double()).sum().float()
-            d_raw = (contrast / s) * g - (contrast * sgx / (s ** 3 * (n - 1))) * (raw - mu)
+            d_raw = _std_normalise_bwd(g, raw, stats, contrast)
         grad = torch.empty(gen.synth.numel, dtype=torch.float32, device=raw.device)
         gen.synth.backward(d_raw.contiguous(), grad)
         return (None, None, None, None, None, *[v.clone() for v in gen.synth.views(grad)])

@@ -87,6 +87,20 @@ def test_plain_image_f_and_pixel_image_grads():
     q = prm[0].detach().cpu().requires_grad_(True)
     (R.synth_pixel(q, R.colcorr_t(2.0), 0.9) * gw).sum().backward()
     assert (prm[0].grad.cpu() - q.grad).abs().max().item() < 1e-4 * q.grad.abs().max().item()
+    # the plain DWT path (DWTImage.__call__): the same reference expression on the inverse transform, the gradient of all coefficients
+    from aphantasia_amd.image import dwt_image
+    from oracle import dwt_ref
+    seed_all(1)
+    Ys, dwt_f, _ = dwt_image([1, 3, 24, 40], 'db3', 0.3, 1.8, None)
+    out = dwt_f(contrast=1.2)
+    gd = torch.randn(out.shape)
+    (out * gd.to(DEV)).sum().backward()
+    ys = [y.detach().cpu().requires_grad_(True) for y in Ys]
+    want = R.std_normalise(dwt_ref.dwt_image_raw(ys, 'db3', 0.3), 1.2)
+    assert want.shape == out.shape
+    (want * gd).sum().backward()
+    got, ref = torch.cat([y.grad.cpu().reshape(-1) for y in Ys]), torch.cat([y.grad.reshape(-1) for y in ys])
+    assert (got - ref).abs().max().item() < 1e-4 * ref.abs().max().item()
 
 
 def test_loss_curve_vs_oracle_free_running(model):
