@@ -9,10 +9,16 @@
 // output tile in LDS once and every coefficient / pixel is read from HBM exactly once.  One launch per level for the
 // levels that fill the chip; the coarse tail (every level whose output is a single tile) runs in ONE launch, a
 // workgroup per channel walking the levels (aph_idwt_fwd / aph_idwt_bwd).
+//
+// Each filter sum is written once and called by the per-level tile and by the coarse-tail kernel: idwt_hpass / idwt_vpass
+// (forward), idwt_adjoint_hpass / idwt_adjoint_vpass (adjoint); the callers differ in addressing and in where the gain is
+// applied only.  Every kernel and tile takes the filter length LT as its template argument (0: run-time length);
+// idwt_for_length is the one place that maps a run-time L to an instantiation, idwt_geom the one that does a level's sizes.
 #include "aph_device.h"
 #include "aph_host.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace aph {
 
@@ -23,22 +29,102 @@ constexpr int DC_IY = 40, DC_IX = 64;                  //   adjoint: coefficient
 constexpr int DC_MAX_LEVELS = 12;
 constexpr int DC_HS_MAX = 12 * DC_NT;                  // detail-band values of all coarse levels together (one prefetch batch: 12 per thread)
 
+// output length of one sfb1d: n coefficients, filter length L
+__host__ __device__ constexpr int idwt_out(int n, int L) { return 2 * n - L + 2; }
+
+// ---- the filter sums (LT = filter length at compile time, 0: the run-time L) ----------------------------------------------------
+// rec_lo / rec_hi into LDS
+template <int NT>
+__device__ __forceinline__ void idwt_stage_taps(float* f0, float* f1, const float* g0, const float* g1, int L) {
+  for (int k = threadIdx.x; k < L; k += NT) { f0[k] = g0[k]; f1[k] = g1[k]; }
+}
+
+// forward, horizontal: outputs 2j and 2j+1 read the same L/2 inputs i = j + L/2 - 1 - t with the even / odd filter taps:
+// lo = g0 * ll + g1 * HL, hi = g0 * LH + g1 * HH.  in(t) returns that input's (ll, LH, HL, HH), detail bands with their gain.
+template <int LT, class In>
+__device__ __forceinline__ void idwt_hpass(const float* f0, const float* f1, int L, In in, float* lo, float* hi) {
+  float lo_e = 0.f, lo_o = 0.f, hi_e = 0.f, hi_o = 0.f;
+#pragma unroll
+  for (int t = 0; t < (LT ? LT : L) / 2; ++t) {
+    const float a_e = f0[2 * t], a_o = f0[2 * t + 1], b_e = f1[2 * t], b_o = f1[2 * t + 1];
+    const float4 v = in(t);
+    const float vll = v.x, vlh = v.y, vhl = v.z, vhh = v.w;
+    lo_e += a_e * vll + b_e * vhl; lo_o += a_o * vll + b_o * vhl;
+    hi_e += a_e * vlh + b_e * vhh; hi_o += a_o * vlh + b_o * vhh;
+  }
+  *reinterpret_cast<float2*>(lo) = make_float2(lo_e, lo_o);      // (8-byte aligned at every caller)
+  *reinterpret_cast<float2*>(hi) = make_float2(hi_e, hi_o);
+}
+
+// forward, vertical: out = g0 * rlo + g1 * rhi for the output row pair (even, odd); rlo / rhi point at input row (rl + L/2 - 1),
+// rows `pitch` apart.  V = float: one column; V = float4: four columns (16-byte LDS reads), the same sum in each component.
+// (The float4 operands go by value and the sums live in locals: through references the L = 6 kernel took 98 VGPRs instead of 60.)
+__device__ __forceinline__ void idwt_mac2(float& o, float a, float lo, float b, float hi) { o += a * lo + b * hi; }
+__device__ __forceinline__ void idwt_mac2(float4& o, float a, float4 lo, float b, float4 hi) {
+  o.x += a * lo.x + b * hi.x; o.y += a * lo.y + b * hi.y; o.z += a * lo.z + b * hi.z; o.w += a * lo.w + b * hi.w;
+}
+template <int LT, class V>
+__device__ __forceinline__ void idwt_vpass(const float* f0, const float* f1, int L, const float* rlo, const float* rhi, int pitch, V& r_e, V& r_o) {
+  V o_e = V(), o_o = o_e;
+#pragma unroll
+  for (int t = 0; t < (LT ? LT : L) / 2; ++t) {
+    const V lo = *reinterpret_cast<const V*>(rlo - t * pitch), hi = *reinterpret_cast<const V*>(rhi - t * pitch);
+    const float a_e = f0[2 * t], a_o = f0[2 * t + 1], b_e = f1[2 * t], b_o = f1[2 * t + 1];
+    idwt_mac2(o_e, a_e, lo, b_e, hi);
+    idwt_mac2(o_o, a_o, lo, b_o, hi);
+  }
+  r_e = o_e; r_o = o_o;
+}
+
+// adjoint, horizontal: slo = sum_k g0[k] d[2 ix + k], shi with g1.  in(t) returns (d[2 ix + 2 t], d[2 ix + 2 t + 1]), 0 outside.
+template <int LT, class In>
+__device__ __forceinline__ void idwt_adjoint_hpass(const float* f0, const float* f1, int L, In in, float* slo, float* shi) {
+  float a = 0.f, b = 0.f;
+#pragma unroll
+  for (int t = 0; t < (LT ? LT : L) / 2; ++t) {
+    const float2 v = in(t);
+    a += f0[2 * t] * v.x; a += f0[2 * t + 1] * v.y;
+    b += f1[2 * t] * v.x; b += f1[2 * t + 1] * v.y;
+  }
+  *slo = a;
+  *shi = b;
+}
+
+// adjoint, vertical: (dll, dLH, dHL, dHH) = (sum g0 slo, sum g1 slo, sum g0 shi, sum g1 shi) over rows 2 iyl + k of column ixl
+template <int LT>
+__device__ __forceinline__ float4 idwt_adjoint_vpass(const float* f0, const float* f1, int L, const float* slo, const float* shi, int iyl, int ixl, int pitch) {
+  float all = 0.f, alh = 0.f, ahl = 0.f, ahh = 0.f;
+#pragma unroll
+  for (int k = 0; k < (LT ? LT : L); ++k) {
+    const int e = (2 * iyl + k) * pitch + ixl;
+    const float lo = slo[e], hi = shi[e];
+    all += f0[k] * lo; alh += f1[k] * lo;
+    ahl += f0[k] * hi; ahh += f1[k] * hi;
+  }
+  return make_float4(all, alh, ahl, ahh);
+}
+// the detail-band gradients of idwt_adjoint_vpass, with the level's gain, into [3][h][w] at oh
+__device__ __forceinline__ void idwt_store_highs(float* oh, int h, int w, const float4& a, float hscale) {
+  oh[0] = a.y * hscale;
+  oh[(size_t)h * w] = a.z * hscale;
+  oh[2 * (size_t)h * w] = a.w * hscale;
+}
+
 // Forward tile, separable in LDS: a TY x TX output tile of one channel by NT threads.
 //   1. the four band patches [PY][PX] (PY = TY/2 + L/2 input rows, PX likewise; zero beyond h / w) are loaded once --
 //      with a compile-time filter length EVERY load of the patch is issued before the first LDS write (one memory round
 //      trip per tile; the row loop this replaces waited for memory once per 64 columns of a row, ten times per wave, and
 //      a workgroup's lifetime was those waits: 3.3 TB/s on the finest 4K level);
-//   2. horizontal pass, one thread per (patch row, output column PAIR): outputs 2j and 2j+1 read the same L/2 inputs
-//      i = j + L/2 - 1 - t with the even / odd filter taps:  rlo = g0 * ll + g1 * HL,  rhi = g0 * LH + g1 * HH;
-//   3. vertical pass: out = g0 * rlo + g1 * rhi; four columns of a row pair per thread (16-byte LDS reads and stores)
-//      when the output rows are 16-byte aligned, else one column per thread.
+//   2. horizontal pass (idwt_hpass), one thread per (patch row, output column PAIR);
+//   3. vertical pass (idwt_vpass): four columns of a row pair per thread (16-byte LDS reads and stores) when the output rows
+//      are 16-byte aligned, else one column per thread.
 // bll: [llh][llw] (only rows < h / cols < w are used -- the "unpad" of DWTInverse.forward), bh: [3][h][w] (LH, HL, HH),
-// bout: [Ho][Wo], Ho = 2h-L+2, Wo = 2w-L+2 -- all of ONE channel.  H2T = L/2 at compile time (0: run-time length).
+// bout: [Ho][Wo], Ho = idwt_out(h), Wo = idwt_out(w) -- all of ONE channel.
 // No __restrict__: the coarse-tail kernel reads what its previous level wrote.
-template <int H2T, int TY, int TX, int NT>
+template <int LT, int TY, int TX, int NT>
 __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw, const float* bh, int h, int w, const float* g0,
                                           const float* g1, int L, float hscale, float* bout, int Ho, int Wo, int my0, int mx0) {
-  const int H2 = H2T ? H2T : (L >> 1);
+  const int H2 = LT ? LT / 2 : (L >> 1);
   const int PY = TY / 2 + H2, PX = TX / 2 + H2;
   float* f0 = reinterpret_cast<float*>(smem);  // rec_lo
   float* f1 = f0 + 2 * H2;                     // rec_hi
@@ -51,8 +137,8 @@ __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw,
   const int tid = threadIdx.x;
   // output m = 2 j + p (p = 0, 1) reads inputs i = j + H2 - 1 - t with tap k = p + 2 t;  the tile's first input is m0 / 2
   const int iy0 = my0 / 2, ix0 = mx0 / 2;
-  if constexpr (H2T > 0) {
-    constexpr int PYc = TY / 2 + H2T, PXc = TX / 2 + H2T, NQ = PYc * PXc, NIT = (NQ + NT - 1) / NT;
+  if constexpr (LT > 0) {
+    constexpr int PYc = TY / 2 + LT / 2, PXc = TX / 2 + LT / 2, NQ = PYc * PXc, NIT = (NQ + NT - 1) / NT;
     float v[NIT][4];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -66,7 +152,7 @@ __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw,
       v[it][2] = bh[(size_t)h * w + o];
       v[it][3] = bh[2 * (size_t)h * w + o];
     }
-    for (int k = tid; k < 2 * H2; k += NT) { f0[k] = g0[k]; f1[k] = g1[k]; }      // (behind the patch loads: same round trip)
+    idwt_stage_taps<NT>(f0, f1, g0, g1, 2 * H2);      // (behind the patch loads: same round trip)
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int q = it * NT + tid;
@@ -81,7 +167,7 @@ __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw,
     }
   } else {
     const int lane = tid & 63, wave = tid >> 6;
-    for (int k = tid; k < 2 * H2; k += NT) { f0[k] = g0[k]; f1[k] = g1[k]; }
+    idwt_stage_taps<NT>(f0, f1, g0, g1, 2 * H2);
     for (int py = wave; py < PY; py += NT / 64) {
       const int iy = iy0 + py;
       for (int px = lane; px < PX; px += 64) {
@@ -100,16 +186,8 @@ __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw,
   for (int q = tid; q < PY * (TX / 2); q += NT) {
     const int py = q / (TX / 2), jl = q - py * (TX / 2);
     const int e0 = py * PX + jl + H2 - 1;
-    float lo_e = 0.f, lo_o = 0.f, hi_e = 0.f, hi_o = 0.f;
-#pragma unroll
-    for (int t = 0; t < (H2T ? H2T : H2); ++t) {
-      const float a_e = f0[2 * t], a_o = f0[2 * t + 1], b_e = f1[2 * t], b_o = f1[2 * t + 1];
-      const float vll = pll[e0 - t], vlh = plh[e0 - t], vhl = phl[e0 - t], vhh = phh[e0 - t];
-      lo_e += a_e * vll + b_e * vhl; lo_o += a_o * vll + b_o * vhl;
-      hi_e += a_e * vlh + b_e * vhh; hi_o += a_o * vlh + b_o * vhh;
-    }
-    *reinterpret_cast<float2*>(rlo + py * TX + 2 * jl) = make_float2(lo_e, lo_o);
-    *reinterpret_cast<float2*>(rhi + py * TX + 2 * jl) = make_float2(hi_e, hi_o);
+    idwt_hpass<LT>(f0, f1, L, [&](int t) { return make_float4(pll[e0 - t], plh[e0 - t], phl[e0 - t], phh[e0 - t]); },
+                   rlo + py * TX + 2 * jl, rhi + py * TX + 2 * jl);
   }
   __syncthreads();
   if (((Wo & 3) | (int)(reinterpret_cast<size_t>(bout) & 15)) == 0) {
@@ -117,14 +195,8 @@ __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw,
     for (int q = tid; q < (TY / 2) * (TX / 4); q += NT) {
       const int rl = q / (TX / 4), c4 = q - rl * (TX / 4), my = my0 + 2 * rl, mx = mx0 + 4 * c4;
       const int e0 = (rl + H2 - 1) * TX + 4 * c4;
-      float4 o_e = make_float4(0.f, 0.f, 0.f, 0.f), o_o = o_e;
-#pragma unroll
-      for (int t = 0; t < (H2T ? H2T : H2); ++t) {
-        const float4 lo = *reinterpret_cast<const float4*>(rlo + e0 - t * TX), hi = *reinterpret_cast<const float4*>(rhi + e0 - t * TX);
-        const float a_e = f0[2 * t], a_o = f0[2 * t + 1], b_e = f1[2 * t], b_o = f1[2 * t + 1];
-        o_e.x += a_e * lo.x + b_e * hi.x; o_e.y += a_e * lo.y + b_e * hi.y; o_e.z += a_e * lo.z + b_e * hi.z; o_e.w += a_e * lo.w + b_e * hi.w;
-        o_o.x += a_o * lo.x + b_o * hi.x; o_o.y += a_o * lo.y + b_o * hi.y; o_o.z += a_o * lo.z + b_o * hi.z; o_o.w += a_o * lo.w + b_o * hi.w;
-      }
+      float4 o_e, o_o;
+      idwt_vpass<LT>(f0, f1, L, rlo + e0, rhi + e0, TX, o_e, o_o);
       if (mx < Wo) {
         if (my < Ho) *reinterpret_cast<float4*>(bout + (size_t)my * Wo + mx) = o_e;
         if (my + 1 < Ho) *reinterpret_cast<float4*>(bout + (size_t)(my + 1) * Wo + mx) = o_o;
@@ -134,13 +206,8 @@ __device__ __forceinline__ void idwt_tile(char* smem, const float* bll, int llw,
     for (int q = tid; q < (TY / 2) * TX; q += NT) {
       const int rl = q / TX, tx_ = q - rl * TX, my = my0 + 2 * rl, mx = mx0 + tx_;
       const int e0 = (rl + H2 - 1) * TX + tx_;
-      float o_e = 0.f, o_o = 0.f;
-#pragma unroll
-      for (int t = 0; t < (H2T ? H2T : H2); ++t) {
-        const float lo = rlo[e0 - t * TX], hi = rhi[e0 - t * TX];
-        o_e += f0[2 * t] * lo + f1[2 * t] * hi;
-        o_o += f0[2 * t + 1] * lo + f1[2 * t + 1] * hi;
-      }
+      float o_e, o_o;
+      idwt_vpass<LT>(f0, f1, L, rlo + e0, rhi + e0, TX, o_e, o_o);
       if (mx < Wo) {
         if (my < Ho) bout[(size_t)my * Wo + mx] = o_e;
         if (my + 1 < Ho) bout[(size_t)(my + 1) * Wo + mx] = o_o;
@@ -152,22 +219,22 @@ template <int TY, int TX>
 constexpr size_t idwt_tile_smem(int L) { return sizeof(float) * (2 * L + 4 * (TY / 2 + L / 2) * (TX / 2 + L / 2) + 2 * (TY / 2 + L / 2) * TX); }
 
 // ll: [C][llh][llw], highs: [C][3][h][w], out: [C][Ho][Wo]; one DW_TY x DW_TX output tile of one channel per workgroup
-template <int H2T>
+template <int LT>
 __global__ __launch_bounds__(DW_NT) void idwt_level_kernel(const float* __restrict__ ll, int llh, int llw,
                                                            const float* __restrict__ highs, int h, int w, const float* __restrict__ g0,
                                                            const float* __restrict__ g1, int L, float hscale, float* __restrict__ out,
                                                            int Ho, int Wo) {
   APH_DYN_SMEM(smem);
   const int c = blockIdx.z;
-  idwt_tile<H2T, DW_TY, DW_TX, DW_NT>(smem, ll + (size_t)c * llh * llw, llw, highs + (size_t)c * 3 * h * w, h, w, g0, g1, L, hscale,
-                                      out + (size_t)c * Ho * Wo, Ho, Wo, blockIdx.y * DW_TY, blockIdx.x * DW_TX);
+  idwt_tile<LT, DW_TY, DW_TX, DW_NT>(smem, ll + (size_t)c * llh * llw, llw, highs + (size_t)c * 3 * h * w, h, w, g0, g1, L, hscale,
+                                     out + (size_t)c * Ho * Wo, Ho, Wo, blockIdx.y * DW_TY, blockIdx.x * DW_TX);
 }
 
 // Adjoint tile, separable in LDS: bdout [Ho][Wo] -> bdll [llh][llw] (extra unpadded row/col = 0) and bdh [3][h][w]
 // (x hscale), one channel.  Coefficient i touches outputs m = 2 i + k - (L - 2), k in [0, L).  Per IY x IX tile:
 //   1. dout patch [PY][PX], PY = 2 IY + L - 2 (all loads in flight together, as in idwt_tile);
-//   2. horizontal: slo[y][ix] = sum_k g0[k] pd[y][2 ix + k], shi with g1 -> LDS [2][PY][IX];
-//   3. vertical:   dll = sum_k g0[k] slo[2 iy + k], dLH = sum g1 slo, dHL = sum g0 shi, dHH = sum g1 shi.
+//   2. horizontal (idwt_adjoint_hpass): slo[y][ix], shi[y][ix] -> LDS [2][PY][IX];
+//   3. vertical (idwt_adjoint_vpass): dll, dLH, dHL, dHH.
 template <int LT, int IY, int IX, int NT>
 __device__ __forceinline__ void idwt_adjoint_tile(char* smem, const float* bd, int Ho, int Wo, int h, int w, const float* g0,
                                                   const float* g1, int L_, float hscale, float* bdll, int llh, int llw, float* bdh,
@@ -192,7 +259,7 @@ __device__ __forceinline__ void idwt_adjoint_tile(char* smem, const float* bd, i
       const bool ok = q < NQ && my >= 0 && my < Ho && mx >= 0 && mx < Wo;
       v[it] = bd[ok ? (size_t)my * Wo + mx : 0];
     }
-    for (int k = tid; k < L; k += NT) { f0[k] = g0[k]; f1[k] = g1[k]; }
+    idwt_stage_taps<NT>(f0, f1, g0, g1, L);
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int q = it * NT + tid;
@@ -202,7 +269,7 @@ __device__ __forceinline__ void idwt_adjoint_tile(char* smem, const float* bd, i
     }
   } else {
     const int lane = tid & 63, wave = tid >> 6;
-    for (int k = tid; k < L; k += NT) { f0[k] = g0[k]; f1[k] = g1[k]; }
+    idwt_stage_taps<NT>(f0, f1, g0, g1, L);
     for (int py = wave; py < PY; py += NT / 64) {
       const int my = my0 + py;
       const bool rowok = my >= 0 && my < Ho;
@@ -216,15 +283,7 @@ __device__ __forceinline__ void idwt_adjoint_tile(char* smem, const float* bd, i
   for (int q = tid; q < PY * IX; q += NT) {
     const int py = q / IX, ixl = q - py * IX;
     const float2* row = reinterpret_cast<const float2*>(pd + py * PX + 2 * ixl);      // 8-byte aligned: PX and 2 L are even
-    float a = 0.f, b = 0.f;
-#pragma unroll
-    for (int t = 0; t < (LT ? LT / 2 : L / 2); ++t) {
-      const float2 v = row[t];
-      a += f0[2 * t] * v.x; a += f0[2 * t + 1] * v.y;
-      b += f1[2 * t] * v.x; b += f1[2 * t + 1] * v.y;
-    }
-    slo[q] = a;
-    shi[q] = b;
+    idwt_adjoint_hpass<LT>(f0, f1, L, [&](int t) { return row[t]; }, slo + q, shi + q);
   }
   __syncthreads();
   for (int q = tid; q < IY * IX; q += NT) {
@@ -232,19 +291,9 @@ __device__ __forceinline__ void idwt_adjoint_tile(char* smem, const float* bd, i
     if (iy >= llh || ix >= llw) continue;
     float* ol = bdll + (size_t)iy * llw + ix;
     if (iy >= h || ix >= w) { *ol = 0.f; continue; }      // the row / column DWTInverse drops
-    float all = 0.f, alh = 0.f, ahl = 0.f, ahh = 0.f;
-#pragma unroll
-    for (int k = 0; k < (LT ? LT : L); ++k) {
-      const int e = (2 * iyl + k) * IX + ixl;
-      const float lo = slo[e], hi = shi[e];
-      all += f0[k] * lo; alh += f1[k] * lo;
-      ahl += f0[k] * hi; ahh += f1[k] * hi;
-    }
-    *ol = all;
-    float* oh = bdh + (size_t)iy * w + ix;
-    oh[0] = alh * hscale;
-    oh[(size_t)h * w] = ahl * hscale;
-    oh[2 * (size_t)h * w] = ahh * hscale;
+    const float4 a = idwt_adjoint_vpass<LT>(f0, f1, L, slo, shi, iyl, ixl, IX);
+    *ol = a.x;
+    idwt_store_highs(bdh + (size_t)iy * w + ix, h, w, a, hscale);
   }
 }
 template <int IY, int IX>
@@ -266,8 +315,7 @@ __global__ __launch_bounds__(DW_NT) void idwt_level_adjoint_kernel(const float* 
 // version that still went through global memory between levels -- load, fence, barrier -- cost 4.7 us per level, hardly less.)
 // Here nothing but the first level's low band, every level's detail bands (all requested up front: one memory round trip for the
 // whole tail) and the last level's output touches global memory: the running low band stays in LDS between levels.  Whole levels
-// need no zero padding: output pair jl reads inputs jl .. jl + L/2 - 1 <= w - 1, rows likewise.  The sums are those of idwt_tile,
-// term for term.
+// need no zero padding: output pair jl reads inputs jl .. jl + L/2 - 1 <= w - 1, rows likewise.
 struct IdwtLevel {                // forward: ll, highs -> out.  adjoint: out = incoming gradient, ll / highs = gradients written
   float* ll; float* highs; float* out;
   int llh, llw, h, w;
@@ -282,10 +330,10 @@ constexpr int DC_R = DC_IY * DC_TX;                   // forward: one horizontal
 inline size_t idwt_coarse_smem(int L, int hsum) { return sizeof(float) * (2 * L + DC_LL + 2 * DC_R + hsum); }
 inline size_t idwt_coarse_adjoint_smem(int L) { return sizeof(float) * (2 * L + DC_LL + DC_IY * DC_IX + 2 * (2 * DC_IY + L - 2) * DC_IX); }
 
-template <int H2T>
+template <int LT>
 __global__ __launch_bounds__(DC_NT) void idwt_coarse_kernel(IdwtLevels lv, const float* __restrict__ g0, const float* __restrict__ g1, int L) {
   APH_DYN_SMEM(smem);
-  constexpr int H2 = H2T;
+  constexpr int H2 = LT / 2;
   float* f0 = reinterpret_cast<float*>(smem);
   float* f1 = f0 + 2 * H2;
   float* LL = f1 + 2 * H2;             // running low band, row pitch `pitch`
@@ -328,7 +376,7 @@ __global__ __launch_bounds__(DC_NT) void idwt_coarse_kernel(IdwtLevels lv, const
       for (int k = 1; k < DC_MAX_LEVELS; ++k) d = qc >= ho[k] ? dk[k] : d;
       v[u] = h0[(ptrdiff_t)d + qc];
     }
-    for (int k = tid; k < 2 * H2; k += DC_NT) { f0[k] = g0[k]; f1[k] = g1[k]; }
+    idwt_stage_taps<DC_NT>(f0, f1, g0, g1, 2 * H2);
     const int n0 = lv.lv[0].llh * lv.lv[0].llw;
 #pragma unroll
     for (int u = 0; u < NLL; ++u) { const int q = u * DC_NT + tid; if (q < n0) LL[q] = wll[u]; }
@@ -342,7 +390,7 @@ __global__ __launch_bounds__(DC_NT) void idwt_coarse_kernel(IdwtLevels lv, const
   int pitch = lv.lv[0].llw;
   for (int i = 0; i < lv.n; ++i) {
     const IdwtLevel& l = lv.lv[i];
-    const int h = l.h, w = l.w, Ho = 2 * h - L + 2, Wo = 2 * w - L + 2, W2 = Wo >> 1;
+    const int h = l.h, w = l.w, Ho = idwt_out(h, L), Wo = idwt_out(w, L), W2 = Wo >> 1;
     const float hsc = l.hscale;
     const float* Hlh = HS + l.hoff;
     const float* Hhl = Hlh + h * w;
@@ -354,16 +402,8 @@ __global__ __launch_bounds__(DC_NT) void idwt_coarse_kernel(IdwtLevels lv, const
       const float* rlh = Hlh + py * w;
       const float* rhl = Hhl + py * w;
       const float* rhh = Hhh + py * w;
-      float lo_e = 0.f, lo_o = 0.f, hi_e = 0.f, hi_o = 0.f;
-#pragma unroll
-      for (int t = 0; t < H2; ++t) {
-        const float a_e = f0[2 * t], a_o = f0[2 * t + 1], b_e = f1[2 * t], b_o = f1[2 * t + 1];
-        const float vll = rll[e0 - t], vlh = rlh[e0 - t] * hsc, vhl = rhl[e0 - t] * hsc, vhh = rhh[e0 - t] * hsc;
-        lo_e += a_e * vll + b_e * vhl; lo_o += a_o * vll + b_o * vhl;
-        hi_e += a_e * vlh + b_e * vhh; hi_o += a_o * vlh + b_o * vhh;
-      }
-      *reinterpret_cast<float2*>(rlo + py * Wo + 2 * jl) = make_float2(lo_e, lo_o);      // (8-byte aligned: Wo is even)
-      *reinterpret_cast<float2*>(rhi + py * Wo + 2 * jl) = make_float2(hi_e, hi_o);
+      idwt_hpass<LT>(f0, f1, L, [&](int t) { return make_float4(rll[e0 - t], rlh[e0 - t] * hsc, rhl[e0 - t] * hsc, rhh[e0 - t] * hsc); },
+                     rlo + py * Wo + 2 * jl, rhi + py * Wo + 2 * jl);      // (8-byte aligned: Wo is even)
     }
     __syncthreads();
     // vertical pass: the level's output is the next level's low band (row pitch Wo); only the last one leaves the CU
@@ -372,13 +412,8 @@ __global__ __launch_bounds__(DC_NT) void idwt_coarse_kernel(IdwtLevels lv, const
     for (int q = tid; q < (Ho >> 1) * Wo; q += DC_NT) {
       const int rl = q / Wo, x = q - rl * Wo;
       const int e0 = (rl + H2 - 1) * Wo + x;
-      float o_e = 0.f, o_o = 0.f;
-#pragma unroll
-      for (int t = 0; t < H2; ++t) {
-        const float lo = rlo[e0 - t * Wo], hi = rhi[e0 - t * Wo];
-        o_e += f0[2 * t] * lo + f1[2 * t] * hi;
-        o_o += f0[2 * t + 1] * lo + f1[2 * t + 1] * hi;
-      }
+      float o_e, o_o;
+      idwt_vpass<LT>(f0, f1, L, rlo + e0, rhi + e0, Wo, o_e, o_o);
       LL[2 * rl * Wo + x] = o_e;
       LL[(2 * rl + 1) * Wo + x] = o_o;
       if (last) { gout[(size_t)2 * rl * Wo + x] = o_e; gout[(size_t)(2 * rl + 1) * Wo + x] = o_o; }
@@ -405,36 +440,31 @@ __global__ __launch_bounds__(DC_NT) void idwt_coarse_adjoint_kernel(IdwtLevels l
     // the tail's only read from global memory: the first level's incoming gradient (<= DC_TY x DC_TX), all loads in flight together
     constexpr int NA = (DC_LL + DC_NT - 1) / DC_NT;
     const IdwtLevel& l0 = lv.lv[0];
-    const int n0 = (2 * l0.h - L + 2) * (2 * l0.w - L + 2);
+    const int n0 = idwt_out(l0.h, L) * idwt_out(l0.w, L);
     const float* src = l0.out + (size_t)c * n0;
     float v[NA];
 #pragma unroll
     for (int u = 0; u < NA; ++u) { const int q = u * DC_NT + tid; v[u] = src[q < n0 ? q : 0]; }
-    for (int k = tid; k < L; k += DC_NT) { f0[k] = g0[k]; f1[k] = g1[k]; }
+    idwt_stage_taps<DC_NT>(f0, f1, g0, g1, L);
 #pragma unroll
     for (int u = 0; u < NA; ++u) { const int q = u * DC_NT + tid; if (q < n0) DA[q] = v[u]; }
   }
   __syncthreads();
   for (int i = 0; i < lv.n; ++i) {
     const IdwtLevel& l = lv.lv[i];
-    const int h = l.h, w = l.w, llh = l.llh, llw = l.llw, Ho = 2 * h - L + 2, Wo = 2 * w - L + 2;
+    const int h = l.h, w = l.w, llh = l.llh, llw = l.llw, Ho = idwt_out(h, L), Wo = idwt_out(w, L);
     const int PY = 2 * llh + L - 2;
     for (int q = tid; q < PY * llw; q += DC_NT) {
       const int py = q / llw, ixl = q - py * llw;
       const int my = py - (L - 2), mxb = 2 * ixl - (L - 2);
       const bool rowok = my >= 0 && my < Ho;
       const float* row = DA + (rowok ? my : 0) * Wo;
-      float a = 0.f, b = 0.f;
-#pragma unroll
-      for (int t = 0; t < L / 2; ++t) {
+      idwt_adjoint_hpass<LT>(f0, f1, L, [&](int t) {
         const int mx = mxb + 2 * t;
         const float vx = (rowok && mx >= 0 && mx < Wo) ? row[mx] : 0.f;
         const float vy = (rowok && mx + 1 >= 0 && mx + 1 < Wo) ? row[mx + 1] : 0.f;
-        a += f0[2 * t] * vx; a += f0[2 * t + 1] * vy;
-        b += f1[2 * t] * vx; b += f1[2 * t + 1] * vy;
-      }
-      slo[q] = a;
-      shi[q] = b;
+        return make_float2(vx, vy);
+      }, slo + q, shi + q);
     }
     __syncthreads();
     const bool last = i + 1 == lv.n;
@@ -447,118 +477,91 @@ __global__ __launch_bounds__(DC_NT) void idwt_coarse_adjoint_kernel(IdwtLevels l
         if (last) gll[q] = 0.f;
         continue;
       }
-      float all = 0.f, alh = 0.f, ahl = 0.f, ahh = 0.f;
-#pragma unroll
-      for (int k = 0; k < L; ++k) {
-        const int e = (2 * iyl + k) * llw + ixl;
-        const float lo = slo[e], hi = shi[e];
-        all += f0[k] * lo; alh += f1[k] * lo;
-        ahl += f0[k] * hi; ahh += f1[k] * hi;
-      }
-      DB[q] = all;
-      if (last) gll[q] = all;
-      float* oh = gh + (size_t)iyl * w + ixl;
-      oh[0] = alh * l.hscale;
-      oh[(size_t)h * w] = ahl * l.hscale;
-      oh[2 * (size_t)h * w] = ahh * l.hscale;
+      const float4 a = idwt_adjoint_vpass<LT>(f0, f1, L, slo, shi, iyl, ixl, llw);
+      DB[q] = a.x;
+      if (last) gll[q] = a.x;
+      idwt_store_highs(gh + (size_t)iyl * w + ixl, h, w, a, l.hscale);
     }
     __syncthreads();
     float* t_ = DA; DA = DB; DB = t_;
   }
 }
 
-template <int H2T>
-void launch_idwt_fwd(dim3 grid, size_t smem, hipStream_t st, const float* d_ll, int ll_h, int ll_w, const float* d_highs, int h, int w,
-                     const float* d_g0, const float* d_g1, int L, float hscale, float* d_out, int Ho, int Wo) {
-  APH_ALLOW_SMEM(idwt_level_kernel<H2T>, 150 * 1024);
-  APH_LAUNCH(idwt_level_kernel<H2T>, grid, dim3(DW_NT), smem, st, d_ll, ll_h, ll_w, d_highs, h, w, d_g0, d_g1, L, hscale, d_out, Ho, Wo);
-}
-template <int LT>
-void launch_idwt_bwd(dim3 grid, size_t smem, hipStream_t st, const float* d_out_grad, int Ho, int Wo, int h, int w, const float* d_g0,
-                     const float* d_g1, int L, float hscale, float* d_ll_grad, int ll_h, int ll_w, float* d_highs_grad) {
-  APH_ALLOW_SMEM(idwt_level_adjoint_kernel<LT>, 150 * 1024);
-  APH_LAUNCH(idwt_level_adjoint_kernel<LT>, grid, dim3(DW_NT), smem, st, d_out_grad, Ho, Wo, h, w, d_g0, d_g1, L, hscale, d_ll_grad, ll_h,
-             ll_w, d_highs_grad);
-}
-template <int H2T>
-void launch_idwt_coarse(const IdwtLevels& lv, int C, size_t smem, hipStream_t st, const float* d_g0, const float* d_g1, int L) {
-  APH_ALLOW_SMEM(idwt_coarse_kernel<H2T>, 150 * 1024);
-  APH_LAUNCH(idwt_coarse_kernel<H2T>, dim3(C), dim3(DC_NT), smem, st, lv, d_g0, d_g1, L);
-}
-template <int LT>
-void launch_idwt_coarse_adjoint(const IdwtLevels& lv, int C, size_t smem, hipStream_t st, const float* d_g0, const float* d_g1, int L) {
-  APH_ALLOW_SMEM(idwt_coarse_adjoint_kernel<LT>, 150 * 1024);
-  APH_LAUNCH(idwt_coarse_adjoint_kernel<LT>, dim3(C), dim3(DC_NT), smem, st, lv, d_g0, d_g1, L);
-}
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+// The filter lengths with an instantiation of their own (fully unrolled filter loops): the common orthogonal wavelets for the
+// per-level kernels, which take every other length at run time (LT = 0); the coarse-tail kernels exist for their list only.
+template <int... Ls> struct IdwtLengths {};
+using IdwtLevelLengths = IdwtLengths<2, 4, 6, 8, 12>;
+using IdwtCoarseLengths = IdwtLengths<2, 4, 6, 8>;
+constexpr size_t kIdwtSmemMax = 150 * 1024;
 
-// filter lengths the coarse-tail kernels are instantiated for (fully unrolled filter loops)
-inline bool idwt_coarse_length(int L) { return L == 2 || L == 4 || L == 6 || L == 8; }
-constexpr size_t kCoarseSmemMax = 150 * 1024;
+// calls f(std::integral_constant<int, LT>) for the LT of the list that equals L; for no such length f(0) if RunTime, else nothing
+template <bool RunTime, int... Ls, class F>
+bool idwt_for_length(int L, IdwtLengths<Ls...>, F f) {
+  const bool hit = ((L == Ls ? (f(std::integral_constant<int, Ls>{}), true) : false) || ...);
+  if constexpr (RunTime) {
+    if (!hit) f(std::integral_constant<int, 0>{});
+  }
+  return hit || RunTime;
+}
+inline bool idwt_coarse_length(int L) { return idwt_for_length<false>(L, IdwtCoarseLengths{}, [](auto) {}); }
 
-void idwt_level_fwd(const float* d_ll, int ll_h, int ll_w, const float* d_highs, int h, int w, int C, const float* d_g0,
-                    const float* d_g1, int L, float hscale, float* d_out, hipStream_t st) {
-  const int Ho = 2 * h - L + 2, Wo = 2 * w - L + 2;
+// One level j of J (0 = finest): detail bands h x w, incoming low band llh x llw, output Ho x Wo
+struct IdwtGeom { int h, w, llh, llw, Ho, Wo; };
+inline IdwtGeom idwt_geom(int h, int w, int llh, int llw, int L) { return IdwtGeom{h, w, llh, llw, idwt_out(h, L), idwt_out(w, L)}; }
+// the running low band that enters level j is the coarsest band itself, else the output of level j + 1
+inline IdwtGeom idwt_geom(const int* hs, const int* ws, int J, int L, int j) {
+  const bool top = j + 1 == J;
+  return idwt_geom(hs[j], ws[j], top ? hs[j] : idwt_out(hs[j + 1], L), top ? ws[j] : idwt_out(ws[j + 1], L), L);
+}
+// ... and it lives in the buffer of level j + 1 (the same choice for its gradient, which level j's adjoint writes)
+template <class T>
+inline T* idwt_ll_of(T* coarsest, float* const* bufs, int J, int j) { return j + 1 < J ? bufs[j + 1] : coarsest; }
+// the gradient that enters level j's adjoint
+inline const float* idwt_grad_in(const float* img_grad, float* const* gbufs, int j) { return j ? gbufs[j] : img_grad; }
+
+void idwt_level_fwd(const float* d_ll, const float* d_highs, const IdwtGeom& g, int C, const float* d_g0, const float* d_g1, int L,
+                    float hscale, float* d_out, hipStream_t st) {
   const size_t smem = idwt_tile_smem<DW_TY, DW_TX>(L);
-  const dim3 grid((Wo + DW_TX - 1) / DW_TX, (Ho + DW_TY - 1) / DW_TY, C);
-#define APH_IDWT_FWD(N) launch_idwt_fwd<N>(grid, smem, st, d_ll, ll_h, ll_w, d_highs, h, w, d_g0, d_g1, L, hscale, d_out, Ho, Wo)
-  switch (L) {            // common orthogonal wavelets get fully unrolled filter loops
-    case 2: APH_IDWT_FWD(1); break;
-    case 4: APH_IDWT_FWD(2); break;
-    case 6: APH_IDWT_FWD(3); break;
-    case 8: APH_IDWT_FWD(4); break;
-    case 12: APH_IDWT_FWD(6); break;
-    default: APH_IDWT_FWD(0); break;
-  }
-#undef APH_IDWT_FWD
+  const dim3 grid((g.Wo + DW_TX - 1) / DW_TX, (g.Ho + DW_TY - 1) / DW_TY, C);
+  idwt_for_length<true>(L, IdwtLevelLengths{}, [&](auto lt) {
+    APH_ALLOW_SMEM(idwt_level_kernel<decltype(lt)::value>, kIdwtSmemMax);
+    APH_LAUNCH(idwt_level_kernel<decltype(lt)::value>, grid, dim3(DW_NT), smem, st, d_ll, g.llh, g.llw, d_highs, g.h, g.w, d_g0, d_g1, L, hscale,
+               d_out, g.Ho, g.Wo);
+  });
 }
-void idwt_level_bwd(const float* d_out_grad, int h, int w, int C, const float* d_g0, const float* d_g1, int L, float hscale,
-                    float* d_ll_grad, int ll_h, int ll_w, float* d_highs_grad, hipStream_t st) {
-  const int Ho = 2 * h - L + 2, Wo = 2 * w - L + 2;
+void idwt_level_bwd(const float* d_out_grad, const IdwtGeom& g, int C, const float* d_g0, const float* d_g1, int L, float hscale,
+                    float* d_ll_grad, float* d_highs_grad, hipStream_t st) {
   const size_t smem = idwt_adjoint_tile_smem<DW_IY, DW_IX>(L);
-  const dim3 grid((ll_w + DW_IX - 1) / DW_IX, (ll_h + DW_IY - 1) / DW_IY, C);
-#define APH_IDWT_BWD(N) launch_idwt_bwd<N>(grid, smem, st, d_out_grad, Ho, Wo, h, w, d_g0, d_g1, L, hscale, d_ll_grad, ll_h, ll_w, d_highs_grad)
-  switch (L) {
-    case 2: APH_IDWT_BWD(2); break;
-    case 4: APH_IDWT_BWD(4); break;
-    case 6: APH_IDWT_BWD(6); break;
-    case 8: APH_IDWT_BWD(8); break;
-    case 12: APH_IDWT_BWD(12); break;
-    default: APH_IDWT_BWD(0); break;
-  }
-#undef APH_IDWT_BWD
+  const dim3 grid((g.llw + DW_IX - 1) / DW_IX, (g.llh + DW_IY - 1) / DW_IY, C);
+  idwt_for_length<true>(L, IdwtLevelLengths{}, [&](auto lt) {
+    APH_ALLOW_SMEM(idwt_level_adjoint_kernel<decltype(lt)::value>, kIdwtSmemMax);
+    APH_LAUNCH(idwt_level_adjoint_kernel<decltype(lt)::value>, grid, dim3(DW_NT), smem, st, d_out_grad, g.Ho, g.Wo, g.h, g.w, d_g0, d_g1, L, hscale,
+               d_ll_grad, g.llh, g.llw, d_highs_grad);
+  });
 }
 void idwt_coarse_fwd(const IdwtLevels& lv, int C, const float* d_g0, const float* d_g1, int L, hipStream_t st) {
   const IdwtLevel& lastl = lv.lv[lv.n - 1];
   const size_t smem = idwt_coarse_smem(L, lastl.hoff + 3 * lastl.h * lastl.w);
-  switch (L) {
-    case 2: launch_idwt_coarse<1>(lv, C, smem, st, d_g0, d_g1, L); break;
-    case 4: launch_idwt_coarse<2>(lv, C, smem, st, d_g0, d_g1, L); break;
-    case 6: launch_idwt_coarse<3>(lv, C, smem, st, d_g0, d_g1, L); break;
-    default: launch_idwt_coarse<4>(lv, C, smem, st, d_g0, d_g1, L); break;      // 8 (idwt_coarse_length)
-  }
+  idwt_for_length<false>(L, IdwtCoarseLengths{}, [&](auto lt) {
+    APH_ALLOW_SMEM(idwt_coarse_kernel<decltype(lt)::value>, kIdwtSmemMax);
+    APH_LAUNCH(idwt_coarse_kernel<decltype(lt)::value>, dim3(C), dim3(DC_NT), smem, st, lv, d_g0, d_g1, L);
+  });
 }
 void idwt_coarse_bwd(const IdwtLevels& lv, int C, const float* d_g0, const float* d_g1, int L, hipStream_t st) {
   const size_t smem = idwt_coarse_adjoint_smem(L);
-  switch (L) {
-    case 2: launch_idwt_coarse_adjoint<2>(lv, C, smem, st, d_g0, d_g1, L); break;
-    case 4: launch_idwt_coarse_adjoint<4>(lv, C, smem, st, d_g0, d_g1, L); break;
-    case 6: launch_idwt_coarse_adjoint<6>(lv, C, smem, st, d_g0, d_g1, L); break;
-    default: launch_idwt_coarse_adjoint<8>(lv, C, smem, st, d_g0, d_g1, L); break;
-  }
+  idwt_for_length<false>(L, IdwtCoarseLengths{}, [&](auto lt) {
+    APH_ALLOW_SMEM(idwt_coarse_adjoint_kernel<decltype(lt)::value>, kIdwtSmemMax);
+    APH_LAUNCH(idwt_coarse_adjoint_kernel<decltype(lt)::value>, dim3(C), dim3(DC_NT), smem, st, lv, d_g0, d_g1, L);
+  });
 }
 
-// size of the running low band that enters level j: the coarsest band itself, else the output of level j + 1
-inline void idwt_ll_size(const int* hs, const int* ws, int J, int L, int j, int* llh, int* llw) {
-  if (j + 1 < J) { *llh = 2 * hs[j + 1] - L + 2; *llw = 2 * ws[j + 1] - L + 2; }
-  else { *llh = hs[j]; *llw = ws[j]; }
-}
 int idwt_check_levels(const char* who, const int* hs, const int* ws, int J, int C, int L) {
   if (!hs || !ws || J < 1 || C < 1 || L < 2 || L > 64 || (L & 1)) return aph_fail(APH_ERR_ARG, "%s: bad argument (J=%d C=%d L=%d)", who, J, C, L);
   for (int j = 0; j < J; ++j) {
-    int llh, llw;
-    idwt_ll_size(hs, ws, J, L, j, &llh, &llw);
-    if (hs[j] < 1 || ws[j] < 1 || 2 * hs[j] - L + 2 < 1 || 2 * ws[j] - L + 2 < 1 || llh < hs[j] || llw < ws[j] || llh > hs[j] + 1 || llw > ws[j] + 1)
-      return aph_fail(APH_ERR_ARG, "%s: level %d is %dx%d but its low band would be %dx%d (filter length %d)", who, j, hs[j], ws[j], llh, llw, L);
+    const IdwtGeom g = idwt_geom(hs, ws, J, L, j);
+    if (g.h < 1 || g.w < 1 || g.Ho < 1 || g.Wo < 1 || g.llh < g.h || g.llw < g.w || g.llh > g.h + 1 || g.llw > g.w + 1)
+      return aph_fail(APH_ERR_ARG, "%s: level %d is %dx%d but its low band would be %dx%d (filter length %d)", who, j, g.h, g.w, g.llh, g.llw, L);
   }
   return APH_OK;
 }
@@ -567,13 +570,16 @@ inline int idwt_coarse_count(const int* hs, const int* ws, int J, int L) {
   if (!idwt_coarse_length(L)) return 0;
   int n = 0, hsum = 0;
   for (int j = J - 1; j >= 0 && n < DC_MAX_LEVELS; --j, ++n) {
-    int llh, llw;
-    idwt_ll_size(hs, ws, J, L, j, &llh, &llw);
-    if (2 * hs[j] - L + 2 > DC_TY || 2 * ws[j] - L + 2 > DC_TX || llh > DC_IY || llw > DC_IX) break;
-    hsum += 3 * hs[j] * ws[j];
-    if (hsum > DC_HS_MAX || idwt_coarse_smem(L, hsum) > kCoarseSmemMax) break;      // (the detail bands of all its levels: one prefetch batch, and they must fit the LDS)
+    const IdwtGeom g = idwt_geom(hs, ws, J, L, j);
+    if (g.Ho > DC_TY || g.Wo > DC_TX || g.llh > DC_IY || g.llw > DC_IX) break;
+    hsum += 3 * g.h * g.w;
+    if (hsum > DC_HS_MAX || idwt_coarse_smem(L, hsum) > kIdwtSmemMax) break;      // (the detail bands of all its levels: one prefetch batch, and they must fit the LDS)
   }
   return n >= 2 ? n : 0;
+}
+// what both per-level entry points ask of their arguments (ptrs: every pointer is set)
+inline bool idwt_level_args_ok(bool ptrs, int h, int w, int C, int L, int ll_h, int ll_w) {
+  return ptrs && h >= 1 && w >= 1 && C >= 1 && L >= 2 && L <= 64 && !(L & 1) && ll_h >= h && ll_w >= w;
 }
 
 }  // namespace aph
@@ -588,10 +594,11 @@ extern "C" {
 int aph_idwt_level_fwd(const float* d_ll, int ll_h, int ll_w, const float* d_highs, int h, int w, int C, const float* d_g0,
                        const float* d_g1, int L, float hscale, float* d_out, void* stream_) {
   APH_TRY
-  if (!d_ll || !d_highs || !d_g0 || !d_g1 || !d_out || h < 1 || w < 1 || C < 1 || L < 2 || L > 64 || (L & 1) || ll_h < h || ll_w < w)
+  if (!idwt_level_args_ok(d_ll && d_highs && d_g0 && d_g1 && d_out, h, w, C, L, ll_h, ll_w))
     return aph_fail(APH_ERR_ARG, "aph_idwt_level_fwd: bad argument (h=%d w=%d L=%d ll=%dx%d)", h, w, L, ll_h, ll_w);
-  if (2 * h - L + 2 < 1 || 2 * w - L + 2 < 1) return aph_fail(APH_ERR_ARG, "aph_idwt_level_fwd: level %dx%d too small for filter length %d", h, w, L);
-  idwt_level_fwd(d_ll, ll_h, ll_w, d_highs, h, w, C, d_g0, d_g1, L, hscale, d_out, (hipStream_t)stream_);
+  const IdwtGeom g = idwt_geom(h, w, ll_h, ll_w, L);
+  if (g.Ho < 1 || g.Wo < 1) return aph_fail(APH_ERR_ARG, "aph_idwt_level_fwd: level %dx%d too small for filter length %d", h, w, L);
+  idwt_level_fwd(d_ll, d_highs, g, C, d_g0, d_g1, L, hscale, d_out, (hipStream_t)stream_);
   return aph_check_launch("aph_idwt_level_fwd");
   APH_CATCH
 }
@@ -599,9 +606,9 @@ int aph_idwt_level_fwd(const float* d_ll, int ll_h, int ll_w, const float* d_hig
 int aph_idwt_level_bwd(const float* d_out_grad, int h, int w, int C, const float* d_g0, const float* d_g1, int L, float hscale,
                        float* d_ll_grad, int ll_h, int ll_w, float* d_highs_grad, void* stream_) {
   APH_TRY
-  if (!d_out_grad || !d_g0 || !d_g1 || !d_ll_grad || !d_highs_grad || h < 1 || w < 1 || C < 1 || L < 2 || L > 64 || (L & 1) || ll_h < h || ll_w < w)
+  if (!idwt_level_args_ok(d_out_grad && d_g0 && d_g1 && d_ll_grad && d_highs_grad, h, w, C, L, ll_h, ll_w))
     return aph_fail(APH_ERR_ARG, "aph_idwt_level_bwd: bad argument");
-  idwt_level_bwd(d_out_grad, h, w, C, d_g0, d_g1, L, hscale, d_ll_grad, ll_h, ll_w, d_highs_grad, (hipStream_t)stream_);
+  idwt_level_bwd(d_out_grad, idwt_geom(h, w, ll_h, ll_w, L), C, d_g0, d_g1, L, hscale, d_ll_grad, d_highs_grad, (hipStream_t)stream_);
   return aph_check_launch("aph_idwt_level_bwd");
   APH_CATCH
 }
@@ -626,22 +633,18 @@ int aph_idwt_fwd(const float* d_yl, const float* const* d_highs, const int* hs, 
     int hoff = 0;
     bool fits = true;
     for (int i = 0; i < nc; ++i, --j) {
-      int llh, llw;
-      idwt_ll_size(hs, ws, J, L, j, &llh, &llw);
+      const IdwtGeom g = idwt_geom(hs, ws, J, L, j);
       const ptrdiff_t delta = d_highs[j] - d_highs[J - 1];      // (in floats; the kernel addresses every level's bands from the first one's pointer)
       if (delta > (ptrdiff_t)0x3fffffff || delta < -(ptrdiff_t)0x3fffffff) { fits = false; break; }
-      lv.lv[i] = IdwtLevel{const_cast<float*>(j + 1 < J ? d_bufs[j + 1] : d_yl), const_cast<float*>(d_highs[j]), d_bufs[j], llh, llw, hs[j], ws[j], hscales[j], hoff,
+      lv.lv[i] = IdwtLevel{const_cast<float*>(idwt_ll_of(d_yl, d_bufs, J, j)), const_cast<float*>(d_highs[j]), d_bufs[j], g.llh, g.llw, g.h, g.w, hscales[j], hoff,
                            (int)delta};
-      hoff += 3 * hs[j] * ws[j];
+      hoff += 3 * g.h * g.w;
     }
     if (fits) idwt_coarse_fwd(lv, C, d_g0, d_g1, L, st);
     else j = J - 1;                      // (detail bands in allocations too far apart for 32-bit offsets: one launch per level)
   }
-  for (; j >= 0; --j) {
-    int llh, llw;
-    idwt_ll_size(hs, ws, J, L, j, &llh, &llw);
-    idwt_level_fwd(j + 1 < J ? d_bufs[j + 1] : d_yl, llh, llw, d_highs[j], hs[j], ws[j], C, d_g0, d_g1, L, hscales[j], d_bufs[j], st);
-  }
+  for (; j >= 0; --j)
+    idwt_level_fwd(idwt_ll_of(d_yl, d_bufs, J, j), d_highs[j], idwt_geom(hs, ws, J, L, j), C, d_g0, d_g1, L, hscales[j], d_bufs[j], st);
   return aph_check_launch("aph_idwt_fwd");
   APH_CATCH
 }
@@ -658,19 +661,15 @@ int aph_idwt_bwd(const float* d_img_grad, const int* hs, const int* ws, const fl
   hipStream_t st = (hipStream_t)stream_;
   const int nc = idwt_coarse_count(hs, ws, J, L);
   int j = 0;
-  for (; j < J - nc; ++j) {
-    int llh, llw;
-    idwt_ll_size(hs, ws, J, L, j, &llh, &llw);
-    idwt_level_bwd(j ? d_gbufs[j] : d_img_grad, hs[j], ws[j], C, d_g0, d_g1, L, hscales[j], j + 1 < J ? d_gbufs[j + 1] : d_yl_grad, llh, llw,
+  for (; j < J - nc; ++j)
+    idwt_level_bwd(idwt_grad_in(d_img_grad, d_gbufs, j), idwt_geom(hs, ws, J, L, j), C, d_g0, d_g1, L, hscales[j], idwt_ll_of(d_yl_grad, d_gbufs, J, j),
                    d_highs_grad[j], st);
-  }
   if (nc) {
     IdwtLevels lv;
     lv.n = nc;
     for (int i = 0; i < nc; ++i, ++j) {
-      int llh, llw;
-      idwt_ll_size(hs, ws, J, L, j, &llh, &llw);
-      lv.lv[i] = IdwtLevel{j + 1 < J ? d_gbufs[j + 1] : d_yl_grad, d_highs_grad[j], const_cast<float*>(j ? d_gbufs[j] : d_img_grad), llh, llw, hs[j], ws[j],
+      const IdwtGeom g = idwt_geom(hs, ws, J, L, j);
+      lv.lv[i] = IdwtLevel{idwt_ll_of(d_yl_grad, d_gbufs, J, j), d_highs_grad[j], const_cast<float*>(idwt_grad_in(d_img_grad, d_gbufs, j)), g.llh, g.llw, g.h, g.w,
                            hscales[j], 0, 0};
     }
     idwt_coarse_bwd(lv, C, d_g0, d_g1, L, st);

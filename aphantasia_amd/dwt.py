@@ -120,31 +120,33 @@ class DWTSynth:
                       self.L, lv['bufs'], ops._stream(flat))
         return self.bufs[0]
 
+    def levels(self, coarsest, bufs):
+        """the level chain, finest first: (j, (h, w) of level j's detail bands, (llh, llw) of the low band that enters it, that band's
+        buffer -- `coarsest` for the last level, else bufs[j + 1], where level j + 1 leaves its output -- and bufs[j], level j's own
+        output).  The forward transform walks it in reverse, low band -> output; the adjoint in order, output gradient -> low-band gradient."""
+        for j in range(self.J):
+            top = j + 1 == self.J
+            yield j, self.sizes[j], (self.sizes[j] if top else self.out_sizes[j + 1]), (coarsest if top else bufs[j + 1]), bufs[j]
+
+    def level_fwd(self, ys, j, hw, llhw, ll, out, st):
+        self.lib.call('aph_idwt_level_fwd', ops.ptr(ll), llhw[0], llhw[1], ops.ptr(ys[1 + j]), hw[0], hw[1], self.C, ops.ptr(self.g0),
+                      ops.ptr(self.g1), self.L, float(self.scale[j]), ops.ptr(out), st)
+
+    def level_bwd(self, gs, j, hw, llhw, dll, dout, st):
+        self.lib.call('aph_idwt_level_bwd', ops.ptr(dout), hw[0], hw[1], self.C, ops.ptr(self.g0), ops.ptr(self.g1), self.L,
+                      float(self.scale[j]), ops.ptr(dll), llhw[0], llhw[1], ops.ptr(gs[1 + j]), st)
+
     def forward_per_level(self, flat):
         """the same transform as one aph_idwt_level_fwd call per level (tests and per-level timing: tools/exp/dwt_levels.py)"""
         ys = self.views(flat)
-        st = ops._stream(flat)
-        ll, llh, llw = ys[0], self.sizes[-1][0], self.sizes[-1][1]
-        for j in range(self.J - 1, -1, -1):
-            hh, ww = self.sizes[j]
-            self.lib.call('aph_idwt_level_fwd', ops.ptr(ll), llh, llw, ops.ptr(ys[1 + j]), hh, ww, self.C, ops.ptr(self.g0),
-                          ops.ptr(self.g1), self.L, float(self.scale[j]), ops.ptr(self.bufs[j]), st)
-            ll, (llh, llw) = self.bufs[j], self.out_sizes[j]
+        for lev in reversed(list(self.levels(ys[0], self.bufs))):
+            self.level_fwd(ys, *lev, ops._stream(flat))
         return self.bufs[0]
 
     def backward_per_level(self, d_raw, grad_flat):
         gs = self.views(grad_flat)
-        st = ops._stream(grad_flat)
-        g = d_raw
-        for j in range(self.J):
-            hh, ww = self.sizes[j]
-            if j + 1 < self.J:
-                dst, (llh, llw) = self.gbufs[j + 1], self.out_sizes[j + 1]
-            else:
-                dst, (llh, llw) = gs[0], self.sizes[-1]
-            self.lib.call('aph_idwt_level_bwd', ops.ptr(g), hh, ww, self.C, ops.ptr(self.g0), ops.ptr(self.g1), self.L,
-                          float(self.scale[j]), ops.ptr(dst), llh, llw, ops.ptr(gs[1 + j]), st)
-            g = dst
+        for lev in self.levels(gs[0], [d_raw] + self.gbufs[1:]):
+            self.level_bwd(gs, *lev, ops._stream(grad_flat))
         return grad_flat
 
     def backward(self, d_raw, grad_flat):
