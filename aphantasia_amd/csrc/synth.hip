@@ -3,12 +3,14 @@
 //   spectrum params --x scale--> column C2C (length H) --> row C2R (length W) --> raw image          synth_fft.h
 //   raw --(global unbiased std, contrast)--> 3x3 colour mix --> sigmoid --> rgb in (0,1)              synth_rgb.h
 //   the RGB priors and the --sharp term on rgb                                                       synth_terms.h
+//   the CPPN generator (cppn.py): network weights --> rgb, and its adjoint                           synth_cppn.h
 //
 // Replaces: aphantasia/image.py:164-175 (fft_image.inner), :21-28 (to_valid_rgb.inner),
 //           :114-118 (pixel_image.inner).  All arithmetic fp32, reductions in fp64.
 #include "synth_fft.h"
 #include "synth_rgb.h"
 #include "synth_terms.h"
+#include "synth_cppn.h"
 
 #include <memory>
 
@@ -103,6 +105,30 @@ static void launch_rgb_bwd(const aph_synth_plan* p, const float* d_rgb, float gs
              p->partials, p->HW());
   APH_LAUNCH(bstats_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)p->partials, kElemBlocks, p->n(), (const float*)p->stats,
              contrast, fixed_div, p->bstats);
+}
+
+// ---- CPPN generator: what both launches share, and one launch helper per kernel (the activation is the kernels' template argument)
+struct CppnArgs {
+  const float *params, *xs, *ys;
+  int W;
+  size_t HW;
+  CppnLayout g;
+  hipStream_t st;
+};
+template <int ACT>
+static void launch_cppn_fwd(const CppnNet& net, const CppnArgs& a, float* stash, float* rgb) {
+  const size_t lds = sizeof(float) * net.fwd_lds();
+  APH_ALLOW_SMEM(cppn_fwd_kernel<ACT>, lds);
+  APH_LAUNCH(cppn_fwd_kernel<ACT>, dim3(a.g.ntiles < kCppnFwdBlocks ? a.g.ntiles : kCppnFwdBlocks), dim3(64 * kCppnWaves), lds, a.st, a.params, net,
+             a.xs, a.ys, a.W, a.HW, stash, rgb, a.g.ntiles);
+}
+template <int ACT>
+static void launch_cppn_bwd(const CppnNet& net, const CppnArgs& a, const float* d_rgb, float gscale, const float* rgb, const float* stash,
+                            float* partials) {
+  const size_t lds = sizeof(float) * net.bwd_lds();
+  APH_ALLOW_SMEM(cppn_bwd_kernel<ACT>, lds);
+  APH_LAUNCH(cppn_bwd_kernel<ACT>, dim3(a.g.bwd_blocks), dim3(64 * kCppnWaves), lds, a.st, a.params, net, a.xs, a.ys, a.W, a.HW, d_rgb, gscale,
+             rgb, stash, partials, net.count(), a.g.ntiles);
 }
 
 extern "C" {
@@ -281,6 +307,53 @@ int aph_rgb_sharp(const float* d_rgb, int H, int W, float weight, void* d_ws, fl
   APH_LAUNCH(rgb_sharp_partial_kernel, dim3(kPriorBlocks), dim3(256), 0, st, d_rgb, H, W, (double*)d_ws);
   APH_LAUNCH(rgb_sharp_apply_kernel, dim3(1024), dim3(256), 0, st, d_rgb, H, W, (const double*)d_ws, kPriorBlocks, weight, d_loss, d_rgb_grad);
   return aph_check_launch("aph_rgb_sharp");
+  APH_CATCH
+}
+
+// ---- CPPN generator (cppn.py:71-116; csrc/synth_cppn.h).  act: 0 unbias, 1 comp, 2 relu.  The library allocates nothing.
+size_t aph_cppn_param_count(int layers, int nf, int act) {
+  if (layers < 1 || layers > kCppnMaxLayers || nf < 1 || nf > kCppnMaxNf || act < 0 || act > 2) return 0;
+  return (size_t)cppn_net(layers, nf, act).count();
+}
+
+size_t aph_cppn_ws_bytes(int layers, int nf, int act, int H, int W) {
+  if (aph_cppn_param_count(layers, nf, act) == 0 || H < 1 || W < 1) return 0;
+  const CppnLayout g = cppn_layout(cppn_net(layers, nf, act), H, W);
+  return sizeof(float) * (g.stash_floats + g.partial_floats);
+}
+
+// params -> d_rgb [3,H,W]; with d_ws also the stash of pre-activations that aph_cppn_bwd reads
+int aph_cppn_fwd(const float* d_params, int layers, int nf, int act, const float* d_xs, const float* d_ys, int H, int W, void* d_ws,
+                 float* d_rgb, void* stream_) {
+  APH_TRY
+  if (!d_params || !d_xs || !d_ys || !d_rgb) return aph_fail(APH_ERR_ARG, "aph_cppn_fwd: null argument");
+  if (int rc = cppn_check_shape("aph_cppn_fwd", layers, nf, act, H, W)) return rc;
+  const CppnNet net = cppn_net(layers, nf, act);
+  const CppnArgs a{d_params, d_xs, d_ys, W, (size_t)H * W, cppn_layout(net, H, W), (hipStream_t)stream_};
+  if (act == 0) launch_cppn_fwd<0>(net, a, (float*)d_ws, d_rgb);
+  else if (act == 1) launch_cppn_fwd<1>(net, a, (float*)d_ws, d_rgb);
+  else launch_cppn_fwd<2>(net, a, (float*)d_ws, d_rgb);
+  return aph_check_launch("aph_cppn_fwd");
+  APH_CATCH
+}
+
+// d_rgb_grad [3,H,W] (times gscale) -> d_grad (flat, the parameters' layout): adjoint of the aph_cppn_fwd that filled d_ws and d_rgb
+int aph_cppn_bwd(const float* d_params, int layers, int nf, int act, const float* d_xs, const float* d_ys, int H, int W,
+                 const float* d_rgb_grad, float gscale, const float* d_rgb, void* d_ws, float* d_grad, void* stream_) {
+  APH_TRY
+  if (!d_params || !d_xs || !d_ys || !d_rgb_grad || !d_rgb || !d_ws || !d_grad)
+    return aph_fail(APH_ERR_ARG, "aph_cppn_bwd: null argument (the workspace of the forward is required)");
+  if (int rc = cppn_check_shape("aph_cppn_bwd", layers, nf, act, H, W)) return rc;
+  const CppnNet net = cppn_net(layers, nf, act);
+  const CppnArgs a{d_params, d_xs, d_ys, W, (size_t)H * W, cppn_layout(net, H, W), (hipStream_t)stream_};
+  float* stash = (float*)d_ws;
+  float* partials = stash + a.g.stash_floats;
+  if (act == 0) launch_cppn_bwd<0>(net, a, d_rgb_grad, gscale, d_rgb, stash, partials);
+  else if (act == 1) launch_cppn_bwd<1>(net, a, d_rgb_grad, gscale, d_rgb, stash, partials);
+  else launch_cppn_bwd<2>(net, a, d_rgb_grad, gscale, d_rgb, stash, partials);
+  const int P = net.count();
+  APH_LAUNCH(cppn_reduce_kernel, dim3((P + 31) / 32), dim3(256), 0, a.st, (const float*)partials, a.g.bwd_blocks, P, d_grad);
+  return aph_check_launch("aph_cppn_bwd");
   APH_CATCH
 }
 

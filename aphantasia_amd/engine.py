@@ -162,9 +162,11 @@ class Engine:
                  lr=0.05, optimizer='adam_custom', align='uniform', macro=0.4, transform=None,
                  size=None, rank=0, world=1, process_group=None, comm=None, param_kind='fft', decorrelate=True, lib=None, state=None, dwt=None, rng='bulk', use_graph=True,
                  rgb_priors=None, fixcontrast=False, sharp=0.0, expand=0.0, enforce=0.0, grad_f16=False, loss_scale=None, reduce_always=False, aest=None,
-                 precise=False, graph_allreduce=None, exact=False):
+                 precise=False, graph_allreduce=None, exact=False, cppn=None):
         """params: the leaf tensor ([1,3,h,w//2+1,2] spectrum for 'fft', [1,3,h,w] for 'pixel', the flat
-        coefficient buffer for 'dwt' with dwt = its aphantasia_amd.dwt.DWTSynth);
+        coefficient buffer for 'dwt' with dwt = its aphantasia_amd.dwt.DWTSynth, the flat weight buffer for 'cppn' with cppn = its
+        aphantasia_amd.cppn.CPPNSynth -- the network's sigmoid output is the image: `colors`, `decay`, `decorrelate`, contrast and shift
+        do not apply, and shift / rgb_priors are refused);
         model: aphantasia_amd.clip.CLIPModel; targets: list of (embedding [1,D] tensor, coef) with
         coef = sign*weight as at clip_fft.py:257-267.
         rng: 'bulk' = vectorised host draws from a numpy Generator seeded off torch's global generator (same
@@ -239,6 +241,13 @@ class Engine:
         self.dwt = dwt
         if param_kind == 'dwt':
             h, w = dwt.H, dwt.W                  # the synthesised image may be one row/col larger than requested
+        self.cppn = cppn
+        if param_kind == 'cppn':
+            if cppn is None or params.numel() != cppn.numel:
+                raise ValueError("Engine: param_kind='cppn' takes cppn = the CPPNSynth whose flat weight buffer `params` is")
+            if rgb_priors is not None:
+                raise NotImplementedError("Engine: rgb_priors are not part of the CPPN path (cppn.py has no such term)")
+            h, w = cppn.H, cppn.W                # (its workspace -- stash and gradient partials -- was allocated with it)
         self.h, self.w = h, w
         # ---- optimiser state; `state=other.state()` shares it (the --dualmod engines, clip_fft.py:243-252)
         self.lr = lr
@@ -362,10 +371,15 @@ class Engine:
             return draw_crop_params_bulk(self.S, self.size, self.h, self.w, self.align, self.macro, self.transform, self.np_rng)
         return draw_crop_params(self.S, self.size, self.h, self.w, self.align, self.macro, self.transform)
 
-    def synthesize(self, contrast=1.0, shift=None):
-        """image_f(shift, contrast) under no_grad (clip_fft.py:239 / :299) -> rgb [3,h,w] (engine-owned buffer)."""
+    def synthesize(self, contrast=1.0, shift=None, for_backward=False):
+        """image_f(shift, contrast) under no_grad (clip_fft.py:239 / :299) -> rgb [3,h,w] (engine-owned buffer).
+        for_backward: the step's own forward ('cppn': it then stashes the pre-activations that _synth_backward reads)."""
         L, st = self.lib, ops._stream(self.params)
-        if self.kind == 'fft':
+        if self.kind == 'cppn':
+            if shift is not None:
+                raise NotImplementedError("Engine: param_kind='cppn' has no spectrum to shift")
+            self.cppn.forward(self.params, out=self.rgb, stash=for_backward)
+        elif self.kind == 'fft':
             L.call('aph_synth_fft_fwd', self.plan.handle, ops.ptr(self.params), ops.ptr(self.scale), ops.ptr(shift), float(contrast),
                    _ffi.floats(self.cc), int(self.decorrelate), ops.ptr(self.raw), ops.ptr(self.rgb), st)
         else:
@@ -400,7 +414,7 @@ class Engine:
         """forward + backward up to the parameter gradient: C-ABI calls only (capturable into a hipGraph)"""
         L, st = self.lib, ops._stream(self.params)
         Sl = self.S_loc
-        self.synthesize(1.0, shift)
+        self.synthesize(1.0, shift, for_backward=True)
         if Sl > 0:
             self._encode_cuts(self.table, self.aug, self.enc)
             L.call('aph_sim_loss', ops.ptr(self.enc), Sl, self.enc.shape[1], ops.ptr(self.targets), ops.ptr(self.dcoef), self.hcoef,
@@ -428,7 +442,9 @@ class Engine:
     def _synth_backward(self, L, st):
         """grgb -> the parameter gradient (adjoint of synthesize)"""
         cc = _ffi.floats(self.cc)
-        if self.kind == 'fft':
+        if self.kind == 'cppn':
+            self.cppn.backward(self.params, self.grgb, self.grad, rgb=self.rgb)
+        elif self.kind == 'fft':
             L.call('aph_synth_fft_bwd', self.plan.handle, ops.ptr(self.grgb), 1.0, ops.ptr(self.rgb), ops.ptr(self.raw), ops.ptr(self.scale),
                    1.0, cc, int(self.decorrelate), ops.ptr(self.grad), st)
         elif self.kind == 'dwt':

@@ -77,6 +77,23 @@ int aph_rgb_priors(const float* d_rgb, int H, int W, float t_mean, float t_std, 
  * d_rgb_grad (both nullable, accumulated); the reference subtracts, so pass weight = -sharp.  d_ws as for aph_rgb_priors. */
 int aph_rgb_sharp(const float* d_rgb, int H, int W, float weight, void* d_ws, float* d_loss, float* d_rgb_grad, void* stream);
 
+/* ---- CPPN generator: the reference's cppn.py:71-116, a coordinate network of 1x1 convolutions whose weights are the
+ * optimised parameters.  Conv(2 -> nf), (layers - 1) x Conv(nhi -> nf), Conv(nhi -> 3) + sigmoid; act 0 `unbias`
+ * (t = atan z; cat[t / 0.67, (t^2 - 0.45) / 0.396]), 1 `comp` (cat[t / 0.67, t^2 / 0.6]), 2 `relu` ((relu z - 0.40) / 0.58);
+ * nhi = 2 nf, relu nf.  d_params: per conv in network order weight[out][in] row-major, then bias[out] (f32; 10 803 floats
+ * for layers 10, nf 24, unbias).  d_xs [W], d_ys [H]: the input coordinates (channel 0 = x along W, channel 1 = y along H).
+ * Supported: 1 <= layers <= 12, 1 <= nf <= 32, any H, W >= 1; else APH_ERR_UNSUPPORTED.  f32 arithmetic on the f32-input
+ * MFMA; no atomics: the same shapes give the same bits.  The workspace is the caller's (aph_cppn_ws_bytes: the stash of
+ * pre-activations, layers * nf * 4 bytes per pixel, plus one gradient partial per workgroup). */
+size_t aph_cppn_param_count(int layers, int nf, int act);
+size_t aph_cppn_ws_bytes(int layers, int nf, int act, int H, int W);
+/* -> d_rgb [3,H,W] in (0,1).  d_ws NULL: no stash (a forward that no backward follows). */
+int aph_cppn_fwd(const float* d_params, int layers, int nf, int act, const float* d_xs, const float* d_ys, int H, int W,
+                 void* d_ws, float* d_rgb, void* stream);
+/* adjoint of the aph_cppn_fwd that filled d_ws and d_rgb: d_rgb_grad [3,H,W] (times gscale) -> d_grad (layout of d_params) */
+int aph_cppn_bwd(const float* d_params, int layers, int nf, int act, const float* d_xs, const float* d_ys, int H, int W,
+                 const float* d_rgb_grad, float gscale, const float* d_rgb, void* d_ws, float* d_grad, void* stream);
+
 /* ---- wavelet parameteriser: aphantasia/image.py:33-80 (dwt_image) over pytorch_wavelets.DWTInverse ------- */
 /* One synthesis level (lowlevel.SFB2D, mode 'symmetric').  d_ll [C,ll_h,ll_w] running low band (ll_h in {h,h+1}:
  * the extra row/col DWTInverse.forward drops is ignored), d_highs [C,3,h,w] = (LH,HL,HH) of this level,
