@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(HERE, 'libaphantasia_hip.so')
 
 APH_OUT_NCHW_RAW, APH_OUT_NCHW_NORM, APH_OUT_PATCH_F16, APH_GRAD_PATCH_F16, APH_OUT_PATCH_F16_HILO, APH_OUT_PATCH_F32 = 0, 1, 2, 3, 4, 5
 APH_AUG_STRIDE = 16
+APH_TF_FAST, APH_TF_CUSTOM, APH_TF_ELASTIC = 0, 1, 2          # chain kind of aph_sample_*_tf
 SIM_TYPES = {'cossim': 0, 'cos': 0, None: 0, 'mix': 1, 'ang': 2, 'dot': 3}
 
 
@@ -55,6 +56,9 @@ _PROTOTYPES = {
     'aph_sample_ws_bytes': (c_size_t, [POINTER(SampleGeom), c_int]),
     'aph_sample_fwd': (c_int, [POINTER(SampleGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'aph_sample_bwd': (c_int, [POINTER(SampleGeom), c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'aph_sample_ws_bytes_tf': (c_size_t, [POINTER(SampleGeom), c_int]),
+    'aph_sample_fwd_tf': (c_int, [POINTER(SampleGeom), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'aph_sample_bwd_tf': (c_int, [POINTER(SampleGeom), c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'aph_triangle_blur': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     'aph_resize_bicubic': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     'aph_flip_w': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

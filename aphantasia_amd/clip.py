@@ -76,8 +76,13 @@ class VisualTransformer:
         return self.handle.forward(patches, S, out, hilo=hilo, f32=f32)
 
     def __call__(self, x):
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.input_resolution or x.shape[3] != self.input_resolution:
-            raise ValueError('encode_image expects [S,3,%d,%d], got %s' % (self.input_resolution, self.input_resolution, tuple(x.shape)))
+        R, p = self.input_resolution, self.patch_size
+        if x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3] == R + 8 and (R + 8 - p) // p + 1 == R // p:
+            # the padded canvas of transforms_custom / transforms_elastic (transforms.py:147-163): upstream's conv1, stride = kernel = patch,
+            # makes R / p patches a side of it and never reads its last 8 rows and columns -- take the window it reads
+            x = x[:, :, :R, :R]
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != R or x.shape[3] != R:
+            raise ValueError('encode_image expects [S,3,%d,%d], got %s' % (R, R, tuple(x.shape)))
         return _Encode.apply(x, self)
 
 

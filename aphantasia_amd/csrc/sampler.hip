@@ -22,6 +22,7 @@
 #include "sampler_crop.h"
 #include "sampler_crop_adjoint.h"
 #include "sampler_warp.h"
+#include "sampler_kornia.h"
 
 namespace aph {
 
@@ -102,6 +103,23 @@ size_t scratch_floats(const Geom& g) { return (size_t)g.S * 4 * g.size * g.size;
 size_t strip_bytes(const Geom& g) { return ((size_t)(8 * (size_t)strip_cap(g) + 8) * sizeof(int) + 255) & ~(size_t)255; }
 int* ws_strips(void* ws, const Geom& g) { return reinterpret_cast<int*>(static_cast<char*>(ws) + tab_bytes(g)); }
 float* ws_scratch(void* ws, const Geom& g) { return reinterpret_cast<float*>(static_cast<char*>(ws) + tab_bytes(g) + strip_bytes(g)); }
+// the kornia-style chains: scratch A as above (custom needs no more), then for elastic the P x P canvas B, P = size + 8 (the adjoint's planar gradient of the rotated canvas)
+size_t canvas_floats(const Geom& g) { const size_t P = (size_t)g.size + 2 * kTfPad; return (size_t)g.S * 4 * P * P; }
+
+// arguments of aph_sample_fwd_tf / aph_sample_bwd_tf beyond check_geom, for the two kornia-style chains
+int check_tf(const aph_sample_geom* g, int tf, int out_mode, const float* aug, const float* h_aug, const char* who) {
+  if (tf != APH_TF_CUSTOM && tf != APH_TF_ELASTIC) return aph_fail(APH_ERR_ARG, "%s: bad chain kind %d (APH_TF_FAST / _CUSTOM / _ELASTIC)", who, tf);
+  if (!aug) return aph_fail(APH_ERR_ARG, "%s: null augment table (the custom / elastic chains draw a rotation and a jitter per cut)", who);
+  if (out_mode >= APH_OUT_PATCH_F16 && g->patch <= 2 * kTfPad)
+    return aph_fail(APH_ERR_ARG, "%s: patch %d <= 8: the %d x %d canvas holds more than %d patches a side, which the positional embedding of a %d-pixel tower does not cover",
+                    who, g->patch, g->size + 2 * kTfPad, g->size + 2 * kTfPad, g->size / g->patch, g->size);
+  for (int s = 0; h_aug && s < g->S; ++s) {
+    const float dx = h_aug[(size_t)s * APH_AUG_STRIDE], dy = h_aug[(size_t)s * APH_AUG_STRIDE + 1];
+    if (!(dx >= 0.f && dx < (float)kTfJitter && dy >= 0.f && dy < (float)kTfJitter && dx == (float)(int)dx && dy == (float)(int)dy))
+      return aph_fail(APH_ERR_ARG, "%s: cut %d: jitter (dx, dy) = (%g, %g) outside 0 .. %d", who, s, dx, dy, kTfJitter - 1);
+  }
+  return APH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -174,6 +192,64 @@ int aph_sample_bwd(const aph_sample_geom* gg, const void* gout, float gscale, co
   APH_LAUNCH(persp_adjoint_kernel, grid, block, 0, st, (const float*)dB, aug, dA, n);
   rc = launch_crop_adjoint<APH_OUT_NCHW_RAW>((const void*)dA, gscale, table, grgb, g, tab, st);
   return rc ? rc : aph_check_launch("aph_sample_bwd");
+  APH_CATCH
+}
+
+size_t aph_sample_ws_bytes_tf(const aph_sample_geom* gg, int tf) {
+  if (tf == APH_TF_FAST) return aph_sample_ws_bytes(gg, 1);
+  if (!gg || gg->S < 1 || gg->size < 1 || gg->Hp < 1 || gg->Wp < 1 || (tf != APH_TF_CUSTOM && tf != APH_TF_ELASTIC)) return 0;
+  const Geom g = to_geom(gg);
+  return tab_bytes(g) + strip_bytes(g) + (scratch_floats(g) + (tf == APH_TF_ELASTIC ? canvas_floats(g) : 0)) * sizeof(float);
+}
+
+int aph_sample_fwd_tf(const aph_sample_geom* gg, int tf, const float* rgb, const int32_t* table_, const float* aug, const float* h_aug,
+                      void* ws, void* out, int out_mode, void* stream_) {
+  if (tf == APH_TF_FAST) return aph_sample_fwd(gg, rgb, table_, aug, ws, out, out_mode, stream_);
+  APH_TRY
+  if (int e = check_geom(gg, out_mode, "aph_sample_fwd_tf")) return e;
+  if (int e = check_tf(gg, tf, out_mode, aug, h_aug, "aph_sample_fwd_tf")) return e;
+  if (!rgb || !table_ || !out || !ws) return aph_fail(APH_ERR_ARG, "aph_sample_fwd_tf: null argument (the workspace of aph_sample_ws_bytes_tf is required)");
+  hipStream_t st = (hipStream_t)stream_;
+  const Geom g = to_geom(gg);
+  const int n = g.size, P = n + 2 * kTfPad, side = out_mode >= APH_OUT_PATCH_F16 ? n : P;      // patch-major: the top-left window
+  float* A = ws_scratch(ws, g);
+  const dim3 grid((side + 31) / 32, (side + 7) / 8, g.S), block(256);
+  launch_crop_resize<APH_SCRATCH_HWC4>(rgb, (const int*)table_, (void*)A, g, ws_strips(ws, g), st);
+  bool ok;
+  if (tf == APH_TF_CUSTOM) {
+    ok = dispatch_out(FwdModes{}, out_mode, [&](auto m) { APH_LAUNCH(custom_emit_kernel<decltype(m)::value>, grid, block, 0, st, (const float*)A, aug, out, n, g.patch); });
+  } else {
+    ok = dispatch_out(FwdModes{}, out_mode, [&](auto m) { APH_LAUNCH(elastic_emit_kernel<decltype(m)::value>, grid, block, 0, st, (const float*)A, aug, out, n, g.patch); });
+  }
+  if (!ok) return aph_fail(APH_ERR_ARG, "aph_sample_fwd_tf: no kernel for out_mode %d", out_mode);
+  return aph_check_launch("aph_sample_fwd_tf");
+  APH_CATCH
+}
+
+int aph_sample_bwd_tf(const aph_sample_geom* gg, int tf, const void* gout, float gscale, const int32_t* table_, const float* aug,
+                      const float* h_aug, void* ws, float* grgb, int out_mode, void* stream_) {
+  if (tf == APH_TF_FAST) return aph_sample_bwd(gg, gout, gscale, table_, aug, ws, grgb, out_mode, stream_);
+  APH_TRY
+  if (int e = check_geom(gg, out_mode, "aph_sample_bwd_tf", APH_GRAD_PATCH_F16)) return e;
+  if (int e = check_tf(gg, tf, out_mode, aug, h_aug, "aph_sample_bwd_tf")) return e;
+  if (out_mode == APH_OUT_PATCH_F32) out_mode = APH_OUT_PATCH_F16;      // the same gradient layout: f32 patch-major
+  if (!gout || !table_ || !grgb || !ws) return aph_fail(APH_ERR_ARG, "aph_sample_bwd_tf: null argument (the workspace of aph_sample_ws_bytes_tf is required)");
+  hipStream_t st = (hipStream_t)stream_;
+  const Geom g = to_geom(gg);
+  const int n = g.size, P = n + 2 * kTfPad;
+  float* dA = ws_scratch(ws, g);
+  float* dB = dA + scratch_floats(g);
+  const dim3 grid((n + 31) / 32, (n + 7) / 8, g.S), canvas((P + 31) / 32, (P + 7) / 8, g.S), block(256);
+  bool ok;
+  if (tf == APH_TF_CUSTOM) {
+    ok = dispatch_out(GradModes{}, out_mode, [&](auto m) { APH_LAUNCH(custom_adjoint_kernel<decltype(m)::value>, grid, block, 0, st, gout, aug, dA, n, g.patch); });
+  } else {
+    ok = dispatch_out(GradModes{}, out_mode, [&](auto m) { APH_LAUNCH(resample_adjoint_kernel<decltype(m)::value>, canvas, block, 0, st, gout, aug, dB, n, g.patch); });
+    if (ok) APH_LAUNCH(rotate_canvas_adjoint_kernel, grid, block, 0, st, (const float*)dB, aug, dA, n);
+  }
+  if (!ok) return aph_fail(APH_ERR_ARG, "aph_sample_bwd_tf: no kernel for out_mode %d", out_mode);
+  const int rc = launch_crop_adjoint<APH_OUT_NCHW_RAW>((const void*)dA, gscale, (const int*)table_, grgb, g, static_cast<AdjEntry*>(ws), st);
+  return rc ? rc : aph_check_launch("aph_sample_bwd_tf");
   APH_CATCH
 }
 

@@ -235,6 +235,7 @@ class Engine:
         self.np_rng = np.random.default_rng(int(torch.randint(0, 2 ** 31 - 1, (1,)).item())) if rng == 'bulk' else None
         self.align, self.macro, self.transform = align, macro, transform
         self.geometric = isinstance(transform, Transform) and transform.geometric
+        self.tf = transform.kind if self.geometric else _ffi.APH_TF_FAST       # chain kind: fast | custom | elastic (aph_sample_*_tf)
         self.cc = colcorr_t(colors).flatten().tolist()
         self.decorrelate = decorrelate
         self.lib = lib if lib is not None else _ffi.lib()
@@ -289,7 +290,7 @@ class Engine:
         self.ws = torch.empty(0, **f32)            # similarity-loss workspace: sized by set_targets
         self.set_targets(targets)
         self.geom = ops.make_geom(h, w, Sl, self.size, self.patch, align)
-        self.tmp = ops.sample_ws(self.geom, self.geometric, self.dev, self.lib)      # engine-owned: tap tables + augmentation scratch
+        self.tmp = ops.sample_ws(self.geom, self.geometric, self.dev, self.lib, self.tf)      # engine-owned: tap tables + augmentation scratch
         if self.enforce != 0:          # second, independently drawn set of cuts of the same image
             self.enc2, self.genc2, self.grgb2 = torch.empty_like(self.enc), torch.empty_like(self.genc), torch.empty_like(self.grgb)
             self.loss2 = torch.zeros(1, **f32)
@@ -390,7 +391,8 @@ class Engine:
 
     def _encode_cuts(self, table, aug, enc):
         """sampler forward (the shard's cuts of self.rgb, patch-major) -> ViT forward -> enc"""
-        self.lib.call('aph_sample_fwd', ctypes.byref(self.geom), ops.ptr(self.rgb), ops.ptr(table), ops.ptr(aug), ops.ptr(self.tmp),
+        # (the chain kind: APH_TF_FAST is aph_sample_fwd itself; rows from pack_aug / draw_bulk are in range by construction, no host copy to check)
+        self.lib.call('aph_sample_fwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.rgb), ops.ptr(table), ops.ptr(aug), None, ops.ptr(self.tmp),
                       ops.ptr(self.patches), self._patch_mode, ops._stream(self.params))
         self.visual._forward_patches(self.patches, self.S_loc, enc, hilo=self.precise, f32=self.exact)
 
@@ -398,7 +400,7 @@ class Engine:
         """ViT input-gradient of the forward just taken -> sampler adjoint -> grgb"""
         vit_scale, smp_scale, gmode = self._grad_modes()
         self.visual.handle.backward(genc, self.S_loc, self.gpatch, vit_scale, f32=self.exact)
-        self.lib.call('aph_sample_bwd', ctypes.byref(self.geom), ops.ptr(self.gpatch), smp_scale, ops.ptr(table), ops.ptr(aug),
+        self.lib.call('aph_sample_bwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.gpatch), smp_scale, ops.ptr(table), ops.ptr(aug), None,
                       ops.ptr(self.tmp), ops.ptr(grgb), gmode, ops._stream(self.params))
 
     def _grad_modes(self):

@@ -131,7 +131,8 @@ def make_geom(H, W, S, size, patch=32, align='uniform'):
     return SampleGeom(H, W, Hp, Wp, (Hp - H) // 2, (Wp - W) // 2, S, size, patch)
 
 
-def sample_out_shape(geom, out_mode):
+def sample_out_shape(geom, out_mode, tf=_ffi.APH_TF_FAST):
+    """the custom / elastic chains (tf) emit the padded canvas in the planar modes, [S,3,size+8,size+8]; its top-left window otherwise"""
     if out_mode == _ffi.APH_OUT_PATCH_F32:
         g = geom.size // geom.patch
         return (geom.S * g * g, 3 * geom.patch * geom.patch), torch.float32
@@ -139,38 +140,54 @@ def sample_out_shape(geom, out_mode):
         g = geom.size // geom.patch
         kx = 2 if out_mode == _ffi.APH_OUT_PATCH_F16_HILO else 1           # rows [hi | lo] of the split-precision forward
         return (geom.S * g * g, kx * 3 * geom.patch * geom.patch), torch.float16
-    return (geom.S, 3, geom.size, geom.size), torch.float32
+    side = geom.size + 8 if tf != _ffi.APH_TF_FAST else geom.size
+    return (geom.S, 3, side, side), torch.float32
 
 
-def sample_ws(geom, with_aug, device, lib=None):
-    """caller-owned workspace of one aph_sample_fwd / aph_sample_bwd pair (tap tables + augmentation scratch)"""
+def sample_ws(geom, with_aug, device, lib=None, tf=_ffi.APH_TF_FAST):
+    """caller-owned workspace of one aph_sample_fwd / aph_sample_bwd pair (tap tables + augmentation scratch); tf: the chain kind of
+    a geometric augmentation (aph_sample_ws_bytes_tf: the elastic chain holds a (size+8)-sided canvas per cut)"""
     L = lib if lib is not None else _ffi.lib()
-    n = int(L.cdll.aph_sample_ws_bytes(byref(geom), int(bool(with_aug))))
+    if with_aug and tf != _ffi.APH_TF_FAST:
+        n = int(L.cdll.aph_sample_ws_bytes_tf(byref(geom), int(tf)))
+        if n == 0:
+            raise ValueError('sample_ws: bad geometry or chain kind %r' % (tf,))
+    else:
+        n = int(L.cdll.aph_sample_ws_bytes(byref(geom), int(bool(with_aug))))
     return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
 
 
-def sample_fwd(geom, rgb, table, aug=None, tmp=None, out=None, out_mode=_ffi.APH_OUT_NCHW_NORM, lib=None):
-    """rgb [3,H,W] f32, table int32 [S,3] (device), aug f32 [S,16] (device) or None"""
+def sample_fwd(geom, rgb, table, aug=None, tmp=None, out=None, out_mode=_ffi.APH_OUT_NCHW_NORM, lib=None, tf=_ffi.APH_TF_FAST, h_aug=None):
+    """rgb [3,H,W] f32, table int32 [S,3] (device), aug f32 [S,16] (device) or None; tf: the chain kind the rows of `aug` belong to
+    (aph_sample_fwd_tf), h_aug: their host copy (f32 [S,16] CPU tensor) for the C ABI's range check of the jitter, or None"""
     L = _L(lib, rgb, table, aug)
     _chk(rgb, torch.float32, 'rgb'); _chk(table, torch.int32, 'table')
-    shape, dtype = sample_out_shape(geom, out_mode)
+    shape, dtype = sample_out_shape(geom, out_mode, tf)
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=rgb.device)
     if tmp is None:
-        tmp = sample_ws(geom, aug is not None, rgb.device, L)
-    L.call('aph_sample_fwd', byref(geom), ptr(rgb), ptr(table), ptr(aug), ptr(tmp), ptr(out), int(out_mode), _stream(rgb))
+        tmp = sample_ws(geom, aug is not None, rgb.device, L, tf)
+    L.call('aph_sample_fwd_tf', byref(geom), int(tf), ptr(rgb), ptr(table), ptr(aug), ptr(_host_rows(h_aug)), ptr(tmp), ptr(out), int(out_mode),
+           _stream(rgb))            # (APH_TF_FAST: aph_sample_fwd itself)
     return out
 
 
-def sample_bwd(geom, gout, table, aug=None, tmp=None, out=None, out_mode=_ffi.APH_OUT_NCHW_NORM, gscale=1.0, lib=None):
+def _host_rows(h_aug):
+    if h_aug is not None and (h_aug.is_cuda or h_aug.dtype != torch.float32 or not h_aug.is_contiguous()):
+        raise ValueError('h_aug must be a contiguous f32 CPU tensor')
+    return h_aug
+
+
+def sample_bwd(geom, gout, table, aug=None, tmp=None, out=None, out_mode=_ffi.APH_OUT_NCHW_NORM, gscale=1.0, lib=None, tf=_ffi.APH_TF_FAST,
+               h_aug=None):
     L = _L(lib, gout, table, aug)
     _chk(gout, torch.float16 if out_mode == _ffi.APH_GRAD_PATCH_F16 else torch.float32, 'gout')
     if out is None:
         out = torch.empty(3, geom.H, geom.W, dtype=torch.float32, device=gout.device)
     if tmp is None:
-        tmp = sample_ws(geom, aug is not None, gout.device, L)
-    L.call('aph_sample_bwd', byref(geom), ptr(gout), float(gscale), ptr(table), ptr(aug), ptr(tmp), ptr(out), int(out_mode),
-           _stream(gout))
+        tmp = sample_ws(geom, aug is not None, gout.device, L, tf)
+    L.call('aph_sample_bwd_tf', byref(geom), int(tf), ptr(gout), float(gscale), ptr(table), ptr(aug), ptr(_host_rows(h_aug)), ptr(tmp), ptr(out),
+           int(out_mode), _stream(gout))
     return out
 
 

@@ -1,11 +1,18 @@
 """Host side of the augmentations (drop-in for aphantasia/transforms.py: `normalize`,
-`transforms_fast`).
+`transforms_fast`, `transforms_custom`, `transforms_elastic`).
 
 In the reference a transform is a closure applied to every cut inside slice_imgs' Python loop
 (utils.py:250-251).  Here a transform is a *specification*: slice_imgs draws its random parameters
 on the host -- in the reference's exact order on torch's / numpy's global generators, so a seeded
 run consumes the same random stream -- and the HIP sampler applies all cuts in one launch
-(csrc/sampler.hip).  `-tf custom` / `-tf elastic` (kornia-based, non-default) are not provided.
+(csrc/sampler.hip).
+
+`transforms_custom` / `transforms_elastic` (transforms.py:147-163) are built on kornia upstream; here they are the closed pixel-space
+forms of kornia's call chains on the (size + 8)-sided canvas of pad(4) (csrc/sampler_kornia.h), and their output is that canvas,
+[S,3,size+8,size+8], as upstream.  Upstream's "elastic" is NOT random: random_elastic (transforms.py:17-25) draws a kernel size, a sigma and
+two amplitudes, then hands elastic_transform2d a noise field of zeros, so the displacement is identically zero and what remains is a
+DETERMINISTIC resample (elastic_transform2d's grid_sample of the linspace(-1,1) meshgrid with align_corners=False: a half-pixel blur with
+a 1/(P-1) zoom).  That is reproduced; the draws it wastes are still consumed, in its order.
 """
 import math
 import os
@@ -22,9 +29,18 @@ class Transform:
     """Marker object understood by aphantasia_amd.utils.slice_imgs."""
     geometric = False       # draws per-cut warp / erase parameters
     normalise = True        # CLIP mean/std (transforms.py:106)
+    kind = _ffi.APH_TF_FAST # chain kind of aph_sample_fwd_tf / aph_sample_bwd_tf (geometric transforms)
 
     def draw(self, size):
         return None
+
+    def draw_bulk(self, S, size, rng):
+        """packed f32 [S,16] augment table from a numpy Generator (`--rng bulk`)"""
+        return None
+
+    def out_side(self, size):
+        """side of the cuts the chain hands to encode_image"""
+        return size
 
 
 class _Normalize(Transform):
@@ -45,6 +61,45 @@ class _Fast(Transform):
         prm['angle'] = float(ROT_ANGLES_FAST[np.random.randint(0, len(ROT_ANGLES_FAST))])   # == np.random.choice (same stream), transforms.py:75
         return prm
 
+    def draw_bulk(self, S, size, rng):
+        return draw_fast_bulk(S, size, rng)
+
+
+TF_PAD = 4                 # pad(4, mode="constant", constant_value=0.5), transforms.py:148,157
+TF_JITTER = 8              # jitter(8), transforms.py:152,161
+ROT_ANGLES_KORNIA = list(range(-30, 30)) + 20 * [0]        # transforms.py:150,160
+
+
+class _Kornia(Transform):
+    """pad(4, 0.5) [-> RandomErasing(0.2)] -> random_rotate [-> random_elastic] -> jitter(8) -> normalize (transforms.py:147-163); the
+    bracketed stages are `elastic`'s.  The erase rectangle is drawn on the padded canvas."""
+    geometric = True
+
+    def __init__(self, kind):
+        self.kind = kind
+        self.elastic = kind == _ffi.APH_TF_ELASTIC
+
+    def out_side(self, size):
+        return size + 2 * TF_PAD
+
+    def draw(self, size):
+        P = size + 2 * TF_PAD
+        prm = dict(persp=None, erase=None, angle=0.0)
+        if self.elastic and _RU.uniform_().item() < 0.2:          # T.RandomErasing(0.2): `torch.rand(1) < p`, then get_params on [1,3,P,P]
+            prm['erase'] = _erase_params(P, P)
+        prm['angle'] = float(ROT_ANGLES_KORNIA[np.random.randint(0, len(ROT_ANGLES_KORNIA))])   # == np.random.choice(angles), transforms.py:57
+        if self.elastic:                                          # random_elastic (transforms.py:19-21): four draws that shape a zero field
+            np.random.rand(2)
+            np.random.randint(8, 64)
+            np.random.rand()
+        dx = int(np.random.randint(0, TF_JITTER))                 # == np.random.choice(d), transforms.py:30-31
+        dy = int(np.random.randint(0, TF_JITTER))
+        prm['shift'] = (dx, dy)
+        return prm
+
+    def draw_bulk(self, S, size, rng):
+        return draw_kornia_bulk(S, size, rng, self.elastic)
+
 
 def normalize():
     """transforms.py:102-109"""
@@ -52,6 +107,8 @@ def normalize():
 
 
 transforms_fast = _Fast()
+transforms_custom = _Kornia(_ffi.APH_TF_CUSTOM)
+transforms_elastic = _Kornia(_ffi.APH_TF_ELASTIC)
 
 
 _EXACT_ZERO_ROT = os.environ.get('APH_EXACT_ZERO_ROTATION') == '1'
@@ -139,7 +196,7 @@ def _erase_params(img_h, img_w, scale=(0.02, 0.33), ratio=(0.3, 3.3)):
 
 
 def pack_aug(prms):
-    """list of per-cut dicts (persp / erase / angle) -> f32 [S,16] table for aph_sample_fwd (host tensor)."""
+    """list of per-cut dicts (persp / erase / angle [/ shift]) -> f32 [S,16] table for aph_sample_fwd / aph_sample_fwd_tf (host tensor)."""
     finish_draws(prms)
     t = np.zeros((len(prms), _ffi.APH_AUG_STRIDE), dtype=np.float32)
     for s, p in enumerate(prms):
@@ -148,6 +205,14 @@ def pack_aug(prms):
             t[s, 8] = 1.0
         if p.get('erase') is not None:
             t[s, 9:13] = p['erase']
+        if p.get('shift') is not None:
+            # jitter(8) of the custom / elastic chains.  Upstream's K.translate resamples through a normalised fp32 grid, which moves values
+            # by ~1e-4 although the shift is a whole number of pixels; the sampler shifts indices exactly: a documented deviation far
+            # inside the parity tolerance (as is the copy of the zero-angle cuts below, which in pixel space IS the identity resample).
+            dx, dy = (int(v) for v in p['shift'])
+            if not (0 <= dx < TF_JITTER and 0 <= dy < TF_JITTER):
+                raise ValueError('pack_aug: cut %d: jitter (dx, dy) = (%d, %d) outside 0 .. %d' % (s, dx, dy, TF_JITTER - 1))
+            t[s, 0], t[s, 1] = dx, dy
         ang = p.get('angle')
         if ang is not None:
             rot = math.radians(float(ang))
@@ -187,7 +252,17 @@ def draw_fast_bulk(S, size, rng):
         t[idx, 0:8] = np.linalg.solve(a, b[..., None])[..., 0].astype(np.float32)
         t[idx, 8] = 1.0
     # RandomErasing(p=0.2): up to 10 tries of (area in [.02,.33], log-uniform aspect in [.3,3.3])
-    idx = np.nonzero(rng.random(S) < 0.2)[0]
+    _erase_bulk(t, np.nonzero(rng.random(S) < 0.2)[0], size, rng)
+    # random_rotate_fast
+    ang = np.asarray(ROT_ANGLES_FAST, dtype=np.float64)[rng.integers(0, len(ROT_ANGLES_FAST), size=S)]
+    rot = np.radians(ang)
+    t[:, 13], t[:, 14] = np.cos(rot), np.sin(rot)
+    t[:, 15] = 1.0 if _EXACT_ZERO_ROT else (ang != 0.0)          # 0 degrees: copy instead of an identity resampling (see pack_aug)
+    return t
+
+
+def _erase_bulk(t, idx, size, rng):
+    """erase rectangles on a size x size canvas for the rows `idx` of the packed table t (torchvision's RandomErasing.get_params)"""
     if idx.size:
         n = idx.size
         area = size * size * rng.uniform(0.02, 0.33, size=(n, 10))
@@ -202,12 +277,30 @@ def draw_fast_bulk(S, size, rng):
         ej = np.floor(rng.random(n) * (size - ew + 1)).astype(np.int64)
         sel = idx[any_ok]
         t[sel, 9], t[sel, 10], t[sel, 11], t[sel, 12] = ei[any_ok], ej[any_ok], eh[any_ok], ew[any_ok]
-    # random_rotate_fast
-    ang = np.asarray(ROT_ANGLES_FAST, dtype=np.float64)[rng.integers(0, len(ROT_ANGLES_FAST), size=S)]
+
+
+def draw_kornia_bulk(S, size, rng, elastic):
+    """transforms_custom / transforms_elastic parameters for S cuts at once from a numpy Generator -> packed f32 [S,16] table (rows as
+    pack_aug writes them).  Same distributions as _Kornia.draw, NOT the reference's random stream."""
+    t = np.zeros((S, _ffi.APH_AUG_STRIDE), dtype=np.float32)
+    P = size + 2 * TF_PAD
+    t[:, 0] = rng.integers(0, TF_JITTER, size=S)
+    t[:, 1] = rng.integers(0, TF_JITTER, size=S)
+    if elastic:
+        _erase_bulk(t, np.nonzero(rng.random(S) < 0.2)[0], P, rng)
+    ang = np.asarray(ROT_ANGLES_KORNIA, dtype=np.float64)[rng.integers(0, len(ROT_ANGLES_KORNIA), size=S)]
     rot = np.radians(ang)
     t[:, 13], t[:, 14] = np.cos(rot), np.sin(rot)
-    t[:, 15] = 1.0 if _EXACT_ZERO_ROT else (ang != 0.0)          # 0 degrees: copy instead of an identity resampling (see pack_aug)
+    t[:, 15] = 1.0 if _EXACT_ZERO_ROT else (ang != 0.0)
     return t
+
+
+def draw_custom_bulk(S, size, rng):
+    return draw_kornia_bulk(S, size, rng, False)
+
+
+def draw_elastic_bulk(S, size, rng):
+    return draw_kornia_bulk(S, size, rng, True)
 
 
 # ----------------------------------------------------------------------------- illustrip's per-frame warp

@@ -50,18 +50,17 @@ def draw_crop_params_bulk(count, size, h, w, align, macro, transform, rng):
     table[:, 2] = (r_y * (ph - csize).astype(f32)).astype(np.int32)
     aug = None
     if isinstance(transform, Transform) and transform.geometric:
-        from .transforms import draw_fast_bulk
-        aug = draw_fast_bulk(count, size, rng)
+        aug = transform.draw_bulk(count, size, rng)
     return table, aug
 
 
 class _Slice(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, img, geom, table, aug, out_mode):
+    def forward(ctx, img, geom, table, aug, out_mode, tf=_ffi.APH_TF_FAST):
         rgb = img.reshape(3, geom.H, geom.W).contiguous().float()
-        tmp = ops.sample_ws(geom, aug is not None, rgb.device)
-        out = ops.sample_fwd(geom, rgb, table, aug, tmp, None, out_mode)
-        ctx.geom, ctx.out_mode, ctx.tmp = geom, out_mode, tmp
+        tmp = ops.sample_ws(geom, aug is not None, rgb.device, tf=tf)
+        out = ops.sample_fwd(geom, rgb, table, aug, tmp, None, out_mode, tf=tf)
+        ctx.geom, ctx.out_mode, ctx.tmp, ctx.tf = geom, out_mode, tmp, tf
         ctx.save_for_backward(table, aug if aug is not None else table)
         ctx.has_aug = aug is not None
         ctx.shape = img.shape
@@ -70,8 +69,8 @@ class _Slice(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         table, aug = ctx.saved_tensors
-        d = ops.sample_bwd(ctx.geom, g.contiguous().float(), table, aug if ctx.has_aug else None, ctx.tmp, None, ctx.out_mode)
-        return d.reshape(ctx.shape), None, None, None, None
+        d = ops.sample_bwd(ctx.geom, g.contiguous().float(), table, aug if ctx.has_aug else None, ctx.tmp, None, ctx.out_mode, tf=ctx.tf)
+        return d.reshape(ctx.shape), None, None, None, None, None
 
 
 _RU1 = torch.empty(1)
@@ -118,8 +117,9 @@ def draw_crop_params_multi(count, size, hw_list, align='uniform', macro=0., tran
 
 def slice_imgs(imgs, count, size=224, transform=None, align='uniform', macro=0., patch=32):
     """utils.py:218-254.  imgs: list of [1,3,H,W] CUDA tensors -> list of [count,3,size,size] tensors.
-    transform: None, aphantasia_amd.transforms.normalize(), transforms_fast (fused in the HIP sampler),
-    or any other callable (applied per cut on the un-normalised crops, like upstream)."""
+    transform: None, aphantasia_amd.transforms.normalize(), transforms_fast / transforms_custom / transforms_elastic (fused in the HIP
+    sampler; the last two return the padded canvas [count,3,size+8,size+8], as upstream), or any other callable (applied per cut on the
+    un-normalised crops, like upstream)."""
     for img in imgs:
         if img.dim() != 4 or img.shape[0] != 1 or img.shape[1] != 3:
             raise ValueError('slice_imgs expects [1,3,H,W] images, got %s' % (tuple(img.shape),))
@@ -135,7 +135,7 @@ def slice_imgs(imgs, count, size=224, transform=None, align='uniform', macro=0.,
         aug = pack_aug(augs).to(dev) if augs is not None else None
         if fused:
             mode = _ffi.APH_OUT_NCHW_RAW if transform is None or not transform.normalise else _ffi.APH_OUT_NCHW_NORM
-            sliced.append(_Slice.apply(img, geom, tb, aug, mode))
+            sliced.append(_Slice.apply(img, geom, tb, aug, mode, transform.kind if aug is not None else _ffi.APH_TF_FAST))
         else:
             raw = _Slice.apply(img, geom, tb, None, _ffi.APH_OUT_NCHW_RAW)
             sliced.append(torch.cat([transform(raw[c:c + 1]) for c in range(count)], 0))

@@ -130,6 +130,12 @@ def derate_samples(a):
     return s
 
 
+def pick_transform(name):
+    """-tf none | fast | custom | elastic (clip_fft.py:121-128 upstream) -> the Engine's `transform` argument"""
+    from aphantasia_amd import transforms
+    return {'fast': transforms.transforms_fast, 'custom': transforms.transforms_custom, 'elastic': transforms.transforms_elastic}.get(name) or transforms.normalize()
+
+
 def check_samples(n):
     """upstream, `--samples 1` with the default `-tf fast` derates to int(1 * 0.95) = 0 cuts and dies in torch.cat([])
     (clip_fft.py:169, utils.py:253); say so instead"""
@@ -246,8 +252,6 @@ def main(argv=None):
         np.random.seed(a.seed)
     if not a.model.startswith('ViT'):
         raise SystemExit(' the MI355X path covers the ViT CLIP models (ViT-B/32, ViT-B/16); got %s' % a.model)
-    if a.transform in ('custom', 'elastic'):
-        raise SystemExit(' -tf %s (kornia-based) is not provided; use fast or none' % a.transform)
     from aphantasia_amd import clip as aclip, transforms
     from aphantasia_amd.image import to_valid_rgb, fft_image, dwt_image
     from aphantasia_amd.utils import slice_imgs, sim_func, basename, img_list, img_read, txt_clean
@@ -292,7 +296,7 @@ def main(argv=None):
             embs.append([aclip.text_embedding(model, subtxt), wt])
         return embs
 
-    trform_f = transforms.transforms_fast if 'fast' in a.transform else transforms.normalize()
+    trform_f = pick_transform(a.transform)
     out_name = []
     targets, targets2 = [], []          # (embedding, coef) for model 1 / model 2
     if a.in_txt is not None:

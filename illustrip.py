@@ -12,7 +12,7 @@ illustrip_loop.py).  Built on the fused HIP engine; multi-GPU as clip_fft.py (cu
 `transformers` from a LOCAL checkpoint directory (--depth_weights or APH_DEPTH_WEIGHTS; there is no network here) and is the one
 part of the frame that runs on stock PyTorch.
 Out of this path's scope: multi-line text files with topic interpolation, `latent_anima` motion curves (the motion here is the constant one of `--anima False`), --aest, LPIPS,
--tf custom / elastic, translation.  The flags exist and are refused with a message instead of being silently ignored.
+translation.  The flags exist and are refused with a message instead of being silently ignored.
 """
 import argparse
 import os
@@ -107,6 +107,11 @@ def derate_samples(a):
     return s
 
 
+def check_supported(a):
+    if a.aest != 0:
+        raise SystemExit(' --aest is not part of this path')
+
+
 def _spawn_rank(local_rank, argv, world, port, run_id):
     os.environ.update(RANK=str(local_rank), LOCAL_RANK=str(local_rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1',
                       MASTER_PORT=str(port), APH_RUN_ID=run_id, HSA_ENABLE_IPC_MODE_LEGACY='0')
@@ -135,8 +140,7 @@ def main(argv=None):
         comm = acomm.create(rank, world)
         if rank != 0:
             a.verbose, a.no_save, a.depth_dir = False, True, None            # rank 0 reports and writes the frames / depth maps
-    if a.aest != 0 or a.transform in ('custom', 'elastic'):
-        raise SystemExit(' --aest / -tf custom|elastic are not part of this path')
+    check_supported(a)
     if a.in_txt is None and a.in_txt2 is None:
         raise SystemExit(' give a prompt with -t (a text file with several lines / topic interpolation is not part of this path)')
     for t in (a.in_txt, a.in_txt2, a.in_txt0):
@@ -168,7 +172,7 @@ def main(argv=None):
                 if ':' in sub: sub, wt = sub.split(':')[0], float(sub.split(':')[1])
                 out.append((aclip.text_embedding(m, sub), sign * wt))
         return out
-    trf = transforms.transforms_fast if a.transform == 'fast' else transforms.normalize()
+    trf = clip_fft.pick_transform(a.transform)
     if a.gen == 'RGB':                                                                          # illustrip.py:270-272: pixel_image([1,3,*size], resume) -> randn * sd, sd = 1 (image.py:98-101)
         leaf = torch.randn(1, 3, h, w).cuda().contiguous()
         pk = dict(param_kind='pixel', rgb_priors=True, fixcontrast=a.fixcontrast, decay=1.0)

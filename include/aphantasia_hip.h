@@ -143,7 +143,8 @@ typedef struct aph_sample_geom {
 
 #define APH_AUG_STRIDE 16
 /* per-cut augment row (f32 x 16): [0..7] perspective coeffs, [8] has_perspective, [9..12] erase i,j,h,w
- * (h=0: none), [13] cos(angle), [14] sin(angle), [15] has_rotation (transforms_fast always 1) */
+ * (h=0: none), [13] cos(angle), [14] sin(angle), [15] has_rotation (transforms_fast always 1).  The rows of the custom / elastic chains
+ * (aph_sample_fwd_tf): [0] dx, [1] dy, [8] = 0, [9..12] the erase rectangle on the (size + 8)-sided canvas, [13..15] as here. */
 
 /* bytes of the caller-owned device workspace d_ws of one forward/backward pair on geometry g (per-cut tap tables of the
  * crop adjoint, per-XCD work lists of the forward; with_aug != 0 adds the cut scratch of the geometric augmentations).  The library never allocates in a
@@ -159,6 +160,30 @@ int aph_sample_fwd(const aph_sample_geom* g, const float* d_rgb, const int32_t* 
  * Writes (does not accumulate) d_rgb_grad [3,H,W]. */
 int aph_sample_bwd(const aph_sample_geom* g, const void* d_out_grad, float gscale, const int32_t* d_table,
                    const float* d_aug, void* d_ws, float* d_rgb_grad, int out_mode, void* stream);
+/* The augment chain by kind (`-tf fast | custom | elastic`, transforms.py:147-170).  APH_TF_FAST is the chain above: the three _tf entry
+ * points then forward to aph_sample_ws_bytes(g, 1) / aph_sample_fwd / aph_sample_bwd unchanged.  The two kornia-style chains work on the
+ * P x P canvas of pad(4, constant 0.5), P = size + 8:
+ *   APH_TF_CUSTOM:  pad -> random_rotate -> jitter(8) -> normalize                         (one gather from the crop scratch to the output)
+ *   APH_TF_ELASTIC: pad -> RandomErasing -> random_rotate -> random_elastic -> jitter(8) -> normalize.  Upstream calls elastic_transform2d
+ *                   with zero noise: what it computes is a fixed bilinear resample E[v,u] = R(u P/(P-1) - 0.5, v P/(P-1) - 0.5).
+ *                   (one 16-tap gather forward; the adjoint goes through a P x P gradient canvas in the workspace)
+ * Rotation: kornia warp_affine in pixel space (bilinear, zeros padding, align_corners=True, no ones-mask); jitter: a whole-pixel shift
+ * right / down by (dx, dy), zeros shifted in.  Their augment row (APH_AUG_STRIDE floats, same table):
+ *   [0] dx, [1] dy (integers 0 .. 7), [2..7] unused, [8] = 0, [9..12] erase i,j,h,w ON THE P x P CANVAS (h=0: none; custom has no erase stage and does not read them),
+ *   [13] cos(angle), [14] sin(angle), [15] has_rotation (0: the cut is copied, not resampled).
+ * Output: the planar modes hold the whole canvas, f32 [S,3,P,P]; the patch-major modes hold its top-left size x size window in their usual
+ * shape -- exactly what a stride = kernel = patch convolution reads of a P-sided input ((P - patch) / patch + 1 == size / patch needs
+ * patch > 8, else APH_ERR_ARG); the gradient of the planar modes is [S,3,P,P] likewise.
+ * h_aug: HOST copy of the S rows or NULL; when given, dx / dy are range-checked before any launch (the device table cannot be read
+ * without a synchronisation; the kernels themselves are memory-safe for any value).  The elastic workspace holds a P x P canvas per cut (its adjoint's). */
+#define APH_TF_FAST 0
+#define APH_TF_CUSTOM 1
+#define APH_TF_ELASTIC 2
+size_t aph_sample_ws_bytes_tf(const aph_sample_geom* g, int tf);
+int aph_sample_fwd_tf(const aph_sample_geom* g, int tf, const float* d_rgb, const int32_t* d_table, const float* d_aug, const float* h_aug,
+                      void* d_ws, void* d_out, int out_mode, void* stream);
+int aph_sample_bwd_tf(const aph_sample_geom* g, int tf, const void* d_out_grad, float gscale, const int32_t* d_table, const float* d_aug,
+                      const float* h_aug, void* d_ws, float* d_rgb_grad, int out_mode, void* stream);
 /* illustrip.py:130-138 frame_transform = T.functional.affine(img, angle, shift, scale, shear, fill=0, BILINEAR) of a whole
  * [C,H,W] image (once per frame).  h_inv_matrix6: HOST pointer, row-major 2x3 inverse affine matrix (torchvision's
  * _get_inverse_affine_matrix with the image centre as origin).  d_dst must not alias d_src. */
