@@ -6,7 +6,7 @@ namespace aph {
 
 // bicubic value (all three channels) of resized-cut pixel (i, j): utils.py:248-249
 __device__ __forceinline__ void bicubic3(const float* __restrict__ rgb, const Geom& g, const CutBox& b, int i, int j, float v[3]) {
-  const float sy = b.scale * (float)i, sx = b.scale * (float)j;
+  const float sy = src_index(b.scale, i), sx = src_index(b.scale, j);
   const int y0 = (int)floorf(sy), x0 = (int)floorf(sx);
   float wy[4], wx[4];
   cubic_w(sy - (float)y0, wy);
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(1024) void strip_list_kernel(const int* __restrict_
     const int s = u / groups, rg = u - s * groups;
     const CutBox b = load_cut(table, s, g.size);
     int i = rg * kUnitRows + kUnitRows / 2; i = i > g.size - 1 ? g.size - 1 : i;
-    int yy = (int)floorf(b.scale * (float)i); yy = yy > b.cs - 1 ? b.cs - 1 : yy;
+    int yy = (int)floorf(src_index(b.scale, i)); yy = yy > b.cs - 1 ? b.cs - 1 : yy;
     const int yc = wrap(b.oy + yy - g.py0, g.H);
     const int xcd = (yc / strip_px) & 7;
     const int pos = atomicAdd(&cnt[xcd], 1);            // (order inside a list is irrelevant: units are independent)

@@ -17,7 +17,7 @@ struct AdjEntry { int off[4]; float w[4]; };
 
 // weight of output index i on crop-local source position q (sum over clamped taps; forward arithmetic)
 __device__ __forceinline__ float tap_weight(float scale, int i, int cs, int q) {
-  const float sy = scale * (float)i;
+  const float sy = src_index(scale, i);
   const int y0 = (int)floorf(sy);
   float wv[4];
   cubic_w(sy - (float)y0, wv);

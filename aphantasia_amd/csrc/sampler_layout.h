@@ -47,6 +47,14 @@ __device__ __forceinline__ int wrap(int v, int n) {
 // area_pixel_compute_scale(align_corners=True): (in-1)/(out-1), source index = scale*dst, all fp32
 __device__ __forceinline__ float cut_scale(int cs, int size) { return size > 1 ? (float)(cs - 1) / (float)(size - 1) : 0.f; }
 
+// source index of output index i: the float32 product, ROUNDED before anything is subtracted from it (ATen: real = scale * dst, floor, t = real - floor).
+// Contracted into the subtraction -- fma(scale, i, -floor) -- t comes from the unrounded product and moves by up to half an ulp of the index (8e-6 at
+// index 200): the crop adjoint then missed the coordinate-exact fp64 reference by 5.7 to 26 times the float32 oracle's own error (tests/sampler_checks.py)
+__device__ __forceinline__ float src_index(float scale, int i) {
+#pragma clang fp contract(off)
+  return scale * (float)i;
+}
+
 struct CutBox { int cs, ox, oy; float scale; };
 __device__ __forceinline__ CutBox load_cut(const int* __restrict__ table, int s, int size) {
   CutBox b;

@@ -7,8 +7,12 @@ namespace aph {
 
 struct Tap { int x0, y0; float wx0, wx1, wy0, wy1; };   // weights of x0, x0+1, y0, y0+1
 
+// The grids below are torchvision's float32 operations in their order, every product and sum ROUNDED (fp contract off): fused, a source coordinate
+// moves by a few n 2^-24 pixels, which the coordinate-exact fp64 reference sees as 4 to 11 times the float32 oracle's own error, and the tent form of
+// rotate_emit_adjoint_kernel (separate products) would no longer re-derive the forward's footprint bit for bit (tests/sampler_checks.py)
 // normalised grid coordinate -> bilinear footprint in a w x h image (at::native grid_sampler_unnormalize, align_corners=False)
 __device__ __forceinline__ Tap make_tap(float gx, float gy, int w, int h) {
+#pragma clang fp contract(off)
   const float ix = ((gx + 1.f) * (float)w - 1.f) * 0.5f;
   const float iy = ((gy + 1.f) * (float)h - 1.f) * 0.5f;
   Tap t;
@@ -22,6 +26,7 @@ __device__ __forceinline__ Tap make_tap(float gx, float gy, int n) { return make
 
 // torchvision _perspective_grid: base grid linspace(0.5, n-0.5), theta1 / (0.5 n), theta2, g1/g2 - 1
 __device__ __forceinline__ Tap persp_tap(const float* __restrict__ a, int i, int j, int n) {
+#pragma clang fp contract(off)
   const float x = (float)j + 0.5f, y = (float)i + 0.5f, hn = 0.5f * (float)n;
   const float g1x = x * (a[0] / hn) + y * (a[1] / hn) + (a[2] / hn);
   const float g1y = x * (a[3] / hn) + y * (a[4] / hn) + (a[5] / hn);
@@ -31,6 +36,7 @@ __device__ __forceinline__ Tap persp_tap(const float* __restrict__ a, int i, int
 
 // torchvision _gen_affine_grid with the inverse rotation matrix [cos, sin, 0; -sin, cos, 0]
 __device__ __forceinline__ Tap rot_tap(float cs, float sn, int i, int j, int n) {
+#pragma clang fp contract(off)
   const float x = -(float)n * 0.5f + 0.5f + (float)j, y = -(float)n * 0.5f + 0.5f + (float)i, hn = 0.5f * (float)n;
   const float gx = x * (cs / hn) + y * (sn / hn) + (0.0f / hn);
   const float gy = x * (-sn / hn) + y * (cs / hn) + (0.0f / hn);
@@ -155,6 +161,7 @@ __global__ void rotate_emit_adjoint_kernel(const void* __restrict__ gout, const 
         bool iok[3], jok[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
+#pragma clang fp contract(off)
           const int i = i0 + t, j = j0 + t;
           iok[t] = i >= 0 && i <= n - 1 && i <= i1;
           jok[t] = j >= 0 && j <= n - 1 && j <= j1;
@@ -171,6 +178,7 @@ __global__ void rotate_emit_adjoint_kernel(const void* __restrict__ gout, const 
         size_t off[9];
 #pragma unroll
         for (int d = 0; d < 9; ++d) {
+#pragma clang fp contract(off)
           const int a3 = d / 3, b3 = d % 3;
           const float gx = gxj[b3] + gxi[a3], gy = gyj[b3] + gyi[a3];
           const float ix = ((gx + 1.f) * fn - 1.f) * 0.5f, iy = ((gy + 1.f) * fn - 1.f) * 0.5f;
