@@ -70,6 +70,9 @@ _PROTOTYPES = {
     'aph_patchify_f16_hilo': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_patchify_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_unpatchify_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    'aph_patch_row_elems': (c_int, [c_int]),
+    'aph_patchify_f16_win': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'aph_unpatchify_f32_win': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     'aph_vit_create': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     'aph_vit_destroy': (c_int, [c_void_p]),
     'aph_vit_workspace_bytes': (c_size_t, [c_void_p]),

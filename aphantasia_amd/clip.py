@@ -111,19 +111,34 @@ class CLIPModel:
         return self
 
 
-def load(name='ViT-B/32', device='cuda', jit=False, weights=None, seed=1, max_batch=256, exact=False):
+DEFAULT_MAX_BATCH = {'ViT-L/14': 32}     # cuts the activation arena is first sized for (others: 256); ensure_batch grows it
+
+
+def _report_arena(model):
+    """ViT-L/14 keeps 0.152 GB of activations per cut (profiles/vitl14.txt): say once what the handle reserved"""
+    if model.name in DEFAULT_MAX_BATCH:
+        h = model.visual.handle
+        print(' %s: %.2f GB of device memory for weights and the activations of %d cuts' % (model.name, h.workspace_bytes() / 2 ** 30, h.max_batch),
+              flush=True)
+    return model
+
+
+def load(name='ViT-B/32', device='cuda', jit=False, weights=None, seed=1, max_batch=None, exact=False):
     """-> (model, None).  weights: path to an OpenAI CLIP checkpoint; None = seeded synthetic weights.
-    exact: the fp32 ViT path (f32-input MFMA GEMMs, fp32 attention and activations) -- what the reference computes on the CPU."""
+    exact: the fp32 ViT path (f32-input MFMA GEMMs, fp32 attention and activations) -- what the reference computes on the CPU.
+    max_batch: None = 256 cuts, 32 for ViT-L/14 (0.152 GB of activations per cut; Engine / encode_image grow the arena on demand)."""
+    if max_batch is None:
+        max_batch = DEFAULT_MAX_BATCH.get(name, 256)
     if weights is not None:
         vis, cfg, full = load_openai_checkpoint(weights)
         want = visual_config(name)
         if (cfg['patch_size'], cfg['width'], cfg['layers']) != (want['patch_size'], want['width'], want['layers']):
             raise ValueError('%s does not hold a %s visual tower' % (weights, name))
-        return CLIPModel(name, cfg, vis, full, max_batch, exact=exact), None
+        return _report_arena(CLIPModel(name, cfg, vis, full, max_batch, exact=exact)), None
     cfg = visual_config(name)
     warnings.warn('aphantasia_amd.clip.load(%r): no checkpoint given -> seeded SYNTHETIC weights (seed %d); '
                   'images will not be meaningful, use --clip-weights for real runs' % (name, seed))
-    return CLIPModel(name, cfg, synthetic_visual_weights(cfg, seed), None, max_batch, exact=exact), None
+    return _report_arena(CLIPModel(name, cfg, synthetic_visual_weights(cfg, seed), None, max_batch, exact=exact)), None
 
 
 def text_embedding(model, text, device='cuda'):

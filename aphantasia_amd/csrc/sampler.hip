@@ -62,6 +62,38 @@ __global__ void unpatchify_kernel(const float* __restrict__ g, float* __restrict
   }
 }
 
+
+// Any patch side, with a window (aph_patchify_f16_win / aph_unpatchify_f32_win): the patch-major rows are `kp` >= 3 p^2 elements long, the
+// pad columns written as zero; divisions instead of Layout's shifts -- one pass over 0.6 MB per cut next to a ViT step.
+__global__ void patchify_win_kernel(const float* __restrict__ x, half_t* __restrict__ out, int S, int Rs, int R, int p, int kp) {
+  const int gp = R / p, k3 = 3 * p * p;
+  const size_t n = (size_t)S * gp * gp * kp;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = idx / kp;
+    const int k = (int)(idx - row * kp);
+    float v = 0.f;
+    if (k < k3) {
+      const int s = (int)(row / ((size_t)gp * gp)), pr = (int)(row - (size_t)s * gp * gp), py = pr / gp, px = pr - py * gp;
+      const int pix = k / 3, c = k - pix * 3, iy = pix / p, ix = pix - iy * p;
+      v = x[(((size_t)s * 3 + c) * Rs + (py * p + iy)) * Rs + (px * p + ix)];
+    }
+    out[idx] = (half_t)v;
+  }
+}
+__global__ void unpatchify_win_kernel(const float* __restrict__ g, float* __restrict__ out, int S, int Rs, int R, int p, int kp, float gscale) {
+  const int gp = R / p;
+  const size_t n = (size_t)S * 3 * Rs * Rs;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
+    const Nchw e = nchw_of(idx, Rs);
+    float v = 0.f;
+    if (e.i < R && e.j < R) {
+      const int py = e.i / p, px = e.j / p, iy = e.i - py * p, ix = e.j - px * p;
+      v = g[(((size_t)e.s * gp + py) * gp + px) * kp + (iy * p + ix) * 3 + e.c] * gscale;
+    }
+    out[idx] = v;
+  }
+}
+
 }  // namespace aph
 
 using namespace aph;
@@ -284,6 +316,26 @@ int aph_unpatchify_f32(const float* g, int S, int R, int patch, float gscale, fl
   if (!g || !out || S < 1 || R < 1 || patch < 1 || R % patch) return aph_fail(APH_ERR_ARG, "aph_unpatchify_f32: bad argument");
   APH_LAUNCH(unpatchify_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream_, g, out, S, R, patch, gscale);
   return aph_check_launch("aph_unpatchify_f32");
+  APH_CATCH
+}
+
+int aph_patch_row_elems(int patch) { return patch < 1 || patch > 1024 ? 0 : (3 * patch * patch + 127) / 128 * 128; }
+
+int aph_patchify_f16_win(const float* x, int S, int R_src, int R, int patch, void* out, void* stream_) {
+  APH_TRY
+  if (!x || !out || S < 1 || R < 1 || R_src < R || patch < 1 || patch > 1024 || R % patch)
+    return aph_fail(APH_ERR_ARG, "aph_patchify_f16_win: bad argument (S=%d R_src=%d R=%d patch=%d)", S, R_src, R, patch);
+  APH_LAUNCH(patchify_win_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream_, x, (half_t*)out, S, R_src, R, patch, aph_patch_row_elems(patch));
+  return aph_check_launch("aph_patchify_f16_win");
+  APH_CATCH
+}
+
+int aph_unpatchify_f32_win(const float* g, int S, int R_src, int R, int patch, float gscale, float* out, void* stream_) {
+  APH_TRY
+  if (!g || !out || S < 1 || R < 1 || R_src < R || patch < 1 || patch > 1024 || R % patch)
+    return aph_fail(APH_ERR_ARG, "aph_unpatchify_f32_win: bad argument (S=%d R_src=%d R=%d patch=%d)", S, R_src, R, patch);
+  APH_LAUNCH(unpatchify_win_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream_, g, out, S, R_src, R, patch, aph_patch_row_elems(patch), gscale);
+  return aph_check_launch("aph_unpatchify_f32_win");
   APH_CATCH
 }
 

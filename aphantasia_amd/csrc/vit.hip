@@ -235,6 +235,20 @@ int check_call(const aph_vit* v, const void* in, const void* out, int S, const c
   return check_loaded(v, who);
 }
 
+// a patch side that is no power of two: its patch rows come from aph_patchify_f16_win (padded to aph_patch_row_elems), not from the sampler's
+// patch-major layouts.  The routing rule of the whole stack (ops.patchify / unpatchify, Engine) is this one predicate.
+bool window_patch(int patch) { return (patch & (patch - 1)) != 0; }
+
+// towers only the default f16 path serves: more than 256 tokens (the fp32 attention of vit_attn_f32.h stops there) or a window patch (the
+// sampler's patch-major modes, which emit the [hi | lo] and fp32 operands, need a power-of-two patch)
+int check_f16_only(const aph_vit* v, const char* who, const char* what) {
+  if (v->T > 256) return aph_fail(APH_ERR_UNSUPPORTED, "%s: %s is not available for %d tokens per image (it stops at 256)", who, what, v->T);
+  if (window_patch(v->patch))
+    return aph_fail(APH_ERR_UNSUPPORTED, "%s: %s is not available for patch %d (not a power of two: patch rows of %d elements in %d, made by aph_patchify_f16_win)",
+                    who, what, v->patch, 3 * v->patch * v->patch, v->Kp);
+  return 0;
+}
+
 // a launch of the GEMM family, with its HIP event pair when the profile is on (bench.py roofline); flops = its algorithmic FLOPs
 template <class F>
 void vtimed(aph_vit* v, double flops, hipStream_t st, F&& launch) {
@@ -278,13 +292,21 @@ int aph_vit_create(int input_resolution, int patch_size, int width, int layers, 
   if (!out) return aph_fail(APH_ERR_ARG, "aph_vit_create: null out");
   if (width % 256 || width > 1024 || heads * kHeadDim != width)
     return aph_fail(APH_ERR_UNSUPPORTED, "aph_vit_create: width %d / heads %d unsupported (need head dim 64, width in {256,512,768,1024})", width, heads);
-  if (input_resolution % patch_size || (3 * patch_size * patch_size) % 128 || output_dim < 1 || layers < 1 || max_batch < 1)
+  // a power-of-two patch goes through the sampler's patch-major layouts, whose rows are 3 patch^2 elements and never padded: such a tower
+  // needs 3 patch^2 % 128 == 0 as it always did (patch 8 and below stay refused); any other patch side gets padded rows (window_patch)
+  if (patch_size < 1 || patch_size > 64 || input_resolution % patch_size || (!window_patch(patch_size) && (3 * patch_size * patch_size) % 128) ||
+      output_dim < 1 || layers < 1 || max_batch < 1)
     return aph_fail(APH_ERR_UNSUPPORTED, "aph_vit_create: resolution %d / patch %d unsupported", input_resolution, patch_size);
   auto* v = new aph_vit();
   v->res = input_resolution; v->patch = patch_size; v->D = width; v->L = layers; v->heads = heads; v->E = output_dim;
   const int g = input_resolution / patch_size;
-  v->P = g * g; v->T = v->P + 1; v->Kp = 3 * patch_size * patch_size; v->max_batch = max_batch;
-  if (v->T > 256) { delete v; return aph_fail(APH_ERR_UNSUPPORTED, "aph_vit_create: %d tokens per image not supported", v->T); }
+  v->P = g * g; v->T = v->P + 1; v->Kp = aph_patch_row_elems(patch_size); v->max_batch = max_batch;      // (padded to a multiple of 128: zero weight columns)
+  // Tokens per image: the five-block attention (256 < T <= AT_TMAX) is admitted for the towers this library did not build before -- those
+  // whose patch side is no power of two (ViT-L/14).  A power-of-two-patch tower keeps the limit of 256 it has always had: what was refused
+  // stays refused (tests/test_gpu_kernels.py::test_vit_sequence_lengths[256] pins res 256 / patch 16), and its exact, split-precision and
+  // f16-gradient modes stop at 256 tokens anyway.
+  const int t_max = window_patch(patch_size) ? AT_TMAX : 256;
+  if (v->T > t_max) { delete v; return aph_fail(APH_ERR_UNSUPPORTED, "aph_vit_create: %d tokens per image not supported", v->T); }
   v->layers.resize(layers);
   build_weights(v);
   size_t total = 0;
@@ -315,6 +337,7 @@ int aph_vit_enable_hilo(aph_vit* v) {
   APH_TRY
   if (!v) return aph_fail(APH_ERR_ARG, "aph_vit_enable_hilo: null handle");
   if (v->arena_hilo) return APH_OK;
+  if (const int rc = check_f16_only(v, "aph_vit_enable_hilo", "the split-precision forward")) return rc;
   if (const int rc = check_loaded(v, "aph_vit_enable_hilo")) return rc;
   size_t total = 0;
   carve_hilo(v, nullptr, &total);
@@ -343,6 +366,7 @@ int aph_vit_enable_f32(aph_vit* v) {
   APH_TRY
   if (!v) return aph_fail(APH_ERR_ARG, "aph_vit_enable_f32: null handle");
   if (v->arena_f32) return APH_OK;
+  if (const int rc = check_f16_only(v, "aph_vit_enable_f32", "the exact fp32 path")) return rc;
   if (const int rc = check_loaded(v, "aph_vit_enable_f32")) return rc;
   size_t total = 0;
   carve_f32(v, nullptr, &total);
@@ -376,16 +400,19 @@ int aph_vit_set_weight(aph_vit* v, const char* name, const float* data, size_t c
     if (e.key == name) { w = &e; break; }
   if (!w) return aph_fail(APH_ERR_ARG, "aph_vit_set_weight: unknown key %s", name);
   const size_t rows = w->rows, cols = w->cols;
-  if (count != rows * cols) return aph_fail(APH_ERR_ARG, "aph_vit_set_weight(%s): %zu elements, expected %zu", name, count, rows * cols);
+  const bool conv1 = w->key == "conv1.weight";
+  const size_t pp = (size_t)v->patch * v->patch, expect = conv1 ? rows * 3 * pp : rows * cols;      // (the checkpoint's conv1.weight has no pad columns)
+  if (count != expect) return aph_fail(APH_ERR_ARG, "aph_vit_set_weight(%s): %zu elements, expected %zu", name, count, expect);
   std::vector<float> perm;
-  if (w->key == "conv1.weight") {
-    // [D, 3, p, p] (openai/CLIP) -> K order of the sampler's patch rows: pixel-major, channel fastest (sampler.hip patch_index)
-    const size_t pp = (size_t)v->patch * v->patch;
-    perm.resize(count);
+  if (conv1) {
+    // [D, 3, p, p] (openai/CLIP) -> K order of the sampler's patch rows: pixel-major, channel fastest (sampler.hip patch_index); the pad
+    // columns 3 p^2 .. Kp of a padded row (patch 14) are zero, in W and in the transposed copy made from it
+    perm.assign(rows * cols, 0.f);
     for (size_t d = 0; d < rows; ++d)
       for (size_t c = 0; c < 3; ++c)
-        for (size_t q = 0; q < pp; ++q) perm[d * cols + q * 3 + c] = data[d * cols + c * pp + q];
+        for (size_t q = 0; q < pp; ++q) perm[d * cols + q * 3 + c] = data[d * 3 * pp + c * pp + q];
     data = perm.data();
+    count = rows * cols;
   }
   int rc = 0;
   if (w->h16[0]) {
@@ -405,7 +432,7 @@ int aph_vit_set_weight(aph_vit* v, const char* name, const float* data, size_t c
   APH_CATCH
 }
 
-// encode_image: d_patches f16 [S*P, 3*patch*patch] (patch-major, CLIP-normalised) -> d_enc f32 [S, output_dim]
+// encode_image: d_patches f16 [S*P, Kp] (patch-major, CLIP-normalised; Kp = aph_patch_row_elems(patch)) -> d_enc f32 [S, output_dim]
 // hilo: the SPLIT-PRECISION forward -- d_patches rows are [hi (Kp) | lo (Kp)] (APH_OUT_PATCH_F16_HILO) and the first LayerNorm of every
 // block writes [hi (D) | lo (D)]: the patch-embedding and the QKV GEMMs then run over K = 2 Kp / 2 D against the weights repeated along K,
 // i.e. with ~22 operand bits on the two activations whose f16 rounding dominates the input-gradient error on weights with realistic
@@ -472,7 +499,7 @@ int aph_vit_forward_hilo(aph_vit* v, const void* d_patches_hilo, int S, float* d
 }
 
 // input-gradient of the last aph_vit_forward: d_genc f32 [S, output_dim] (already multiplied by the caller's
-// loss scale) -> d_patch_grad f32 [S*P, 3*patch*patch] multiplied by out_scale (pass 1/loss_scale).
+// loss scale) -> d_patch_grad f32 [S*P, Kp] multiplied by out_scale (pass 1/loss_scale).
 static int vit_backward_impl(aph_vit* v, const float* d_genc, int S, void* d_patch_grad, bool grad_f16, float out_scale, void* stream_) {
   if (const int rc = check_call(v, d_genc, d_patch_grad, S, "aph_vit_backward")) return rc;
   if (v->last_fwd == 2)

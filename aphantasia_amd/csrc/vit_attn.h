@@ -17,6 +17,7 @@
 namespace aph {
 
 constexpr int AT_T = 64;                       // padded sequence length
+constexpr int AT_TMAX = 320;                   // longest sequence of the blocked kernels (NB = 5: CLIP ViT-L/14 has T = 257)
 constexpr int AT_RB = 56;                      // row-major LDS tiles of the one-tile backward keep 56 rows when T <= 56 (ViT-B/32: T = 50)
 __device__ __forceinline__ int slot_of(int n) { return ((n >> 5) << 5) + (((n >> 2) & 3) << 3) + (((n >> 4) & 1) << 2) + (n & 3); }
 
@@ -371,10 +372,10 @@ __global__ __launch_bounds__(256, RB == 56 ? 3 : 2) void attn_bwd_mfma_kernel(co
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Same scheme for 64 < T <= 256 tokens (ViT-B/16: T = 197), NB = ceil(T / 64) blocks of 64 tokens, 8 waves.
+// Same scheme for 64 < T <= 320 tokens (ViT-B/16: T = 197, ViT-L/14: T = 257), NB = ceil(T / 64) blocks of 64 tokens, 8 waves.
 // Row-major operand images are [NB*64][64] (at_off on the global row), transposed slot-permuted images are NB tiles
 // of [64 d][64 slots]; probabilities / dS of a 32-token block are one B fragment, so the second product streams over
-// 32-token blocks.  The forward keeps a query tile's whole score row in registers (<= 16 tiles) -- exact softmax, no
+// 32-token blocks.  The forward keeps a query tile's whole score row in registers (<= 4 NB tiles: 20 at NB = 5) -- exact softmax, no
 // online rescaling.  The backward is one kernel (attn_bwd_one_g_kernel below), key tiles stationary; it recomputes
 // P = exp(S/8 - lse) per 32-block from the saved log-sum-exp.
 // ---------------------------------------------------------------------------------------------------------------
@@ -482,7 +483,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_g_kernel(const half_t* __re
 // The row term D_i = dO_i . O_i is formed while the block's Q / dO rows are staged (threads that are not staging).
 // (Measured and rejected: requesting the NEXT block's rows into registers right behind the phase-1 barrier so that they land under the dQ
 // phase -- 120.9 against 113.3 us at C4's shape, profiles/r05_attn_bwd_one.txt: the in-order vmcnt ties the dQ stores to those loads.)
-// LDS: Q, dO row-major + transposed for ONE 64-query block (32 KiB), K^T (8 NB KiB), dS^T (8 NB KiB), lse / D: 96.5 KiB at NB = 4.
+// LDS: Q, dO row-major + transposed for ONE 64-query block (32 KiB), K^T (8 NB KiB), dS^T (8 NB KiB), lse / D: 96.5 KiB at NB = 4, 112.5 KiB at NB = 5.
 // Two barriers per query block.  Keys / queries past T: as above (zero operand rows, finite p and dS); the dS^T image starts zeroed, so the
 // slots of key tiles nobody computes contribute nothing.
 template <int NB>
@@ -508,16 +509,22 @@ __global__ __launch_bounds__(512) void attn_bwd_one_g_kernel(const half_t* __res
   for (int idx = tid; idx < NB * 64; idx += 512) atg_stage<NB>(base + D, ld, T, nullptr, Kt, idx);
   for (int i = tid; i < NB * 512; i += 512) reinterpret_cast<half8*>(dSb)[i] = half8{0, 0, 0, 0, 0, 0, 0, 0};
   constexpr int NJ = (4 * NB + 7) / 8;                   // key tiles per wave
-  half8 kf[NJ][2], vf[NJ][2];
+  // NB = 5 (NJ = 3): 96 accumulator registers; with the 48 fragment registers resident as well the kernel does not fit 256 VGPRs (136 bytes
+  // of scratch per lane).  There the K / V fragments of a key tile are re-read from global (L2: the item's 80 KiB of K / V rows) once per
+  // (query block, key tile) into the one fragment set kf[0] / vf[0] instead of staying in registers -- same fragments, same products, same order.
+  constexpr bool KV_RESIDENT = NJ <= 2;
+  half8 kf[KV_RESIDENT ? NJ : 1][2], vf[KV_RESIDENT ? NJ : 1][2];
   f32x4 ok[NJ][4], ov[NJ][4];
 #pragma unroll
   for (int jj = 0; jj < NJ; ++jj) {
-    const int j = (wave + 8 * jj) * 16 + c16;
-    const bool live = j < T;
+    if constexpr (KV_RESIDENT) {
+      const int j = (wave + 8 * jj) * 16 + c16;
+      const bool live = j < T;
 #pragma unroll
-    for (int kd = 0; kd < 2; ++kd) {
-      kf[jj][kd] = ld_frag_global(base + (size_t)(live ? j : 0) * ld + D + kd * 32 + g * 8, live);
-      vf[jj][kd] = ld_frag_global(base + (size_t)(live ? j : 0) * ld + 2 * D + kd * 32 + g * 8, live);
+      for (int kd = 0; kd < 2; ++kd) {
+        kf[jj][kd] = ld_frag_global(base + (size_t)(live ? j : 0) * ld + D + kd * 32 + g * 8, live);
+        vf[jj][kd] = ld_frag_global(base + (size_t)(live ? j : 0) * ld + 2 * D + kd * 32 + g * 8, live);
+      }
     }
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) { ok[jj][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; ov[jj][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -553,6 +560,15 @@ __global__ __launch_bounds__(512) void attn_bwd_one_g_kernel(const half_t* __res
       if (jt * 16 < T) {
         const int key = jt * 16 + c16, sl = slot_of(key & 63);
         half_t* dst = dSb + (key >> 6) * 4096 + (sl & 7);
+        const int fj = KV_RESIDENT ? jj : 0;             // fragment set of this key tile
+        if constexpr (!KV_RESIDENT) {
+          const bool live = key < T;
+#pragma unroll
+          for (int kd = 0; kd < 2; ++kd) {
+            kf[0][kd] = ld_frag_global(base + (size_t)(live ? key : 0) * ld + D + kd * 32 + g * 8, live);
+            vf[0][kd] = ld_frag_global(base + (size_t)(live ? key : 0) * ld + 2 * D + kd * 32 + g * 8, live);
+          }
+        }
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
           if (q0 + qb * 32 < T) {
@@ -563,8 +579,8 @@ __global__ __launch_bounds__(512) void attn_bwd_one_g_kernel(const half_t* __res
               const int t16 = qb * 32 + u * 16;
 #pragma unroll
               for (int kd = 0; kd < 2; ++kd) {
-                sq[u] = mfma_16x16x32_f16(at_frag(Qs, t16 + c16, kd * 4 + g), kf[jj][kd], sq[u]);
-                dq[u] = mfma_16x16x32_f16(at_frag(Os, t16 + c16, kd * 4 + g), vf[jj][kd], dq[u]);
+                sq[u] = mfma_16x16x32_f16(at_frag(Qs, t16 + c16, kd * 4 + g), kf[fj][kd], sq[u]);
+                dq[u] = mfma_16x16x32_f16(at_frag(Os, t16 + c16, kd * 4 + g), vf[fj][kd], dq[u]);
               }
               const f32x4 L4 = *reinterpret_cast<const f32x4*>(Ls + t16 + g * 4);
               const f32x4 D4 = *reinterpret_cast<const f32x4*>(Ds + t16 + g * 4);
@@ -630,7 +646,7 @@ __global__ __launch_bounds__(512) void attn_bwd_one_g_kernel(const half_t* __res
 }
 
 // ---------------------------------------------------------------------------------
-// host launchers: T <= 64 one-tile kernels, 64 < T <= 256 the blocked kernels (NB = ceil(T / 64))
+// host launchers: T <= 64 one-tile kernels, 64 < T <= 320 (AT_TMAX) the blocked kernels (NB = ceil(T / 64))
 // ---------------------------------------------------------------------------------
 struct AttnArgs {
   const half_t* qkv; half_t* att; float* lse;        // forward: qkv -> att, lse
@@ -643,7 +659,7 @@ void launch_attn_fwd_g(const AttnArgs& a, hipStream_t st) {
   APH_ALLOW_SMEM((attn_fwd_mfma_g_kernel<NB>), smem);
   APH_LAUNCH((attn_fwd_mfma_g_kernel<NB>), dim3(a.S * a.heads), dim3(512), smem, st, a.qkv, a.att, a.lse, a.T, a.heads);
 }
-// blocked backward (64 < T <= 256): one kernel, P and dS formed once (attn_bwd_one_g_kernel)
+// blocked backward (64 < T <= 320): one kernel, P and dS formed once (attn_bwd_one_g_kernel)
 template <int NB>
 void launch_attn_bwd_g(const AttnArgs& a, hipStream_t st) {
   constexpr size_t smem = (size_t)(4 + 2 * NB) * 8192 + 2 * 64 * sizeof(float);
@@ -656,7 +672,8 @@ inline void launch_attn_fwd(const AttnArgs& a, hipStream_t st) {
   if (T <= AT_T) APH_LAUNCH(attn_fwd_mfma_kernel, dim3(a.S * a.heads), dim3(256), 0, st, a.qkv, a.att, a.lse, T, a.heads);
   else if (T <= 128) launch_attn_fwd_g<2>(a, st);
   else if (T <= 192) launch_attn_fwd_g<3>(a, st);
-  else launch_attn_fwd_g<4>(a, st);
+  else if (T <= 256) launch_attn_fwd_g<4>(a, st);
+  else launch_attn_fwd_g<5>(a, st);
 }
 // workgroups of the persistent one-tile backward: 6 per CU (3 are resident at a time -- its LDS footprint; the second half starts as
 // the first finishes, which evens out the tail: measured 34.6 us one item per workgroup, 32.8 us with 3 per CU, 30.7 us with 6,
@@ -684,7 +701,8 @@ inline void launch_attn_bwd(const AttnArgs& a, hipStream_t st) {
   else if (T <= AT_T) APH_LAUNCH(attn_bwd_mfma_kernel<AT_T>, dim3(attn_bwd_wgs(items)), dim3(256), 0, st, a.qkv, a.datt, (const float*)a.lse, a.dqkv, T, a.heads, items);
   else if (T <= 128) launch_attn_bwd_g<2>(a, st);
   else if (T <= 192) launch_attn_bwd_g<3>(a, st);
-  else launch_attn_bwd_g<4>(a, st);
+  else if (T <= 256) launch_attn_bwd_g<4>(a, st);
+  else launch_attn_bwd_g<5>(a, st);
 }
 
 }  // namespace aph

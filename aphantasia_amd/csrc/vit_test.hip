@@ -137,7 +137,7 @@ int aph_gemm_rs_probe(const void* d_A, const void* d_Bt, int M, int N, int K, vo
 int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_datt, float* /*d_delta*/, void* d_dqkv, int S, int T, int heads,
                   int mode, void* stream_) {
   APH_TRY
-  if (!d_qkv || !d_att || !d_lse || S < 1 || T < 1 || T > 256 || heads < 1 || (mode != 0 && mode != 1) ||
+  if (!d_qkv || !d_att || !d_lse || S < 1 || T < 1 || T > AT_TMAX || heads < 1 || (mode != 0 && mode != 1) ||
       (mode == 1 && (!d_datt || !d_dqkv)))
     return aph_fail(APH_ERR_ARG, "aph_attn_test: bad argument");
   const AttnArgs a{(const half_t*)d_qkv, (half_t*)d_att, d_lse, (const half_t*)d_datt, (half_t*)d_dqkv, S, T, heads};

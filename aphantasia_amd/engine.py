@@ -194,6 +194,15 @@ class Engine:
             raise ValueError('Engine: samples = %d; at least one cut is needed (upstream: torch.cat of an empty list, utils.py:253)' % self.S)
         if exact and (precise or grad_f16):
             raise ValueError('Engine: exact=True is exclusive with precise / grad_f16 (the exact path is fp32 end to end)')
+        # a patch side that is no power of two (ViT-L/14): the sampler's patch-major layouts do not cover it, so the cuts leave the sampler
+        # planar and a window patchify / unpatchify pair stands between it and the ViT (_encode_cuts); f16 operands and f32 gradient only
+        self.win = not ops._pow2(self.patch)
+        if self.win or (self.size // self.patch) ** 2 + 1 > 256:
+            for flag, on in (('exact', exact), ('precise', precise), ('grad_f16', grad_f16)):
+                if on:
+                    raise NotImplementedError('Engine(%s=True): not available for this model (patch %d, %d tokens): the exact, split-precision and '
+                                              'f16-gradient paths need a power-of-two patch and at most 256 tokens; ViT-L/14 runs the default '
+                                              'f16 path only' % (flag, self.patch, (self.size // self.patch) ** 2 + 1))
         self.rank, self.world, self.pg = rank, world, process_group
         # comm: aphantasia_amd.comm.Comm -- RCCL called directly through the C ABI (aph_allreduce_f32) on the step's own stream.
         # Without one the reduction goes through torch.distributed's group (the gloo / CPU test path).
@@ -274,13 +283,17 @@ class Engine:
         self.plan = ops.SynthPlan(3, h, w, lib=self.lib)
         self.scale = fft_scale(h, w, decay).to(self.dev).contiguous() if param_kind == 'fft' else None
         g = self.size // self.patch
-        self.P, self.Kp = g * g, 3 * self.patch * self.patch
+        self.P, self.Kp = g * g, ops.patch_row_elems(self.patch)      # (the padded row length: 640 for patch 14)
         D = self.visual.output_dim
         Sl = max(self.S_loc, 1)
         self.raw = torch.empty(3, h, w, **f32)
         self.rgb = torch.empty(3, h, w, **f32)
         self.patches = torch.empty(Sl * self.P, (2 if self.precise else 1) * self.Kp, dtype=torch.float32 if self.exact else torch.float16, device=self.dev)
         self.gpatch = torch.empty(Sl * self.P, self.Kp, dtype=torch.float16 if self.grad_f16 else torch.float32, device=self.dev)
+        if self.win:           # the planar cuts and their gradient: the (size+8)-sided canvas under the custom / elastic chains
+            self.side = self.size + 8 if self.tf != _ffi.APH_TF_FAST else self.size
+            self.cuts = torch.empty(Sl, 3, self.side, self.side, **f32)
+            self.gcuts = torch.empty_like(self.cuts)
         self.enc = torch.empty(Sl, D, **f32)
         self.genc = torch.empty(Sl, D, **f32)
         self.grgb = torch.empty(3, h, w, **f32)
@@ -392,14 +405,28 @@ class Engine:
     def _encode_cuts(self, table, aug, enc):
         """sampler forward (the shard's cuts of self.rgb, patch-major) -> ViT forward -> enc"""
         # (the chain kind: APH_TF_FAST is aph_sample_fwd itself; rows from pack_aug / draw_bulk are in range by construction, no host copy to check)
-        self.lib.call('aph_sample_fwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.rgb), ops.ptr(table), ops.ptr(aug), None, ops.ptr(self.tmp),
-                      ops.ptr(self.patches), self._patch_mode, ops._stream(self.params))
+        st = ops._stream(self.params)
+        if self.win:
+            # planar normalised cuts into the engine's scratch, then the window upstream's conv1 reads (clip.VisualTransformer.__call__) as
+            # padded patch rows: one more pass over 0.6 MB per cut next to the tower's 24 blocks
+            self.lib.call('aph_sample_fwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.rgb), ops.ptr(table), ops.ptr(aug), None, ops.ptr(self.tmp),
+                          ops.ptr(self.cuts), _ffi.APH_OUT_NCHW_NORM, st)
+            self.lib.call('aph_patchify_f16_win', ops.ptr(self.cuts), self.S_loc, self.side, self.size, self.patch, ops.ptr(self.patches), st)
+        else:
+            self.lib.call('aph_sample_fwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.rgb), ops.ptr(table), ops.ptr(aug), None, ops.ptr(self.tmp),
+                          ops.ptr(self.patches), self._patch_mode, st)
         self.visual._forward_patches(self.patches, self.S_loc, enc, hilo=self.precise, f32=self.exact)
 
     def _cuts_backward(self, genc, table, aug, grgb):
         """ViT input-gradient of the forward just taken -> sampler adjoint -> grgb"""
         vit_scale, smp_scale, gmode = self._grad_modes()
         self.visual.handle.backward(genc, self.S_loc, self.gpatch, vit_scale, f32=self.exact)
+        if self.win:
+            st = ops._stream(self.params)
+            self.lib.call('aph_unpatchify_f32_win', ops.ptr(self.gpatch), self.S_loc, self.side, self.size, self.patch, 1.0, ops.ptr(self.gcuts), st)
+            self.lib.call('aph_sample_bwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.gcuts), smp_scale, ops.ptr(table), ops.ptr(aug), None,
+                          ops.ptr(self.tmp), ops.ptr(grgb), _ffi.APH_OUT_NCHW_NORM, st)
+            return
         self.lib.call('aph_sample_bwd_tf', ctypes.byref(self.geom), self.tf, ops.ptr(self.gpatch), smp_scale, ops.ptr(table), ops.ptr(aug), None,
                       ops.ptr(self.tmp), ops.ptr(grgb), gmode, ops._stream(self.params))
 

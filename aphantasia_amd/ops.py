@@ -191,13 +191,31 @@ def sample_bwd(geom, gout, table, aug=None, tmp=None, out=None, out_mode=_ffi.AP
     return out
 
 
-def patchify(x, patch, lib=None, hilo=False, f32=False):
+def patch_row_elems(patch):
+    """aph_patch_row_elems: elements of one patch-major row, round_up(3 patch^2, 128) -- 3072 / 768 for patch 32 / 16, 640 for patch 14"""
+    patch = int(patch)
+    return 0 if patch < 1 else (3 * patch * patch + 127) // 128 * 128
+
+
+def _pow2(patch):
+    return patch >= 1 and patch & (patch - 1) == 0
+
+
+def patchify(x, patch, lib=None, hilo=False, f32=False, R=None):
     """NCHW f32 -> the patch-embed GEMM operand; hilo: rows [hi | lo] for VitHandle.forward(..., hilo=True);
-    f32: fp32 rows (values unchanged) for VitHandle.forward(..., f32=True)"""
+    f32: fp32 rows (values unchanged) for VitHandle.forward(..., f32=True).  A patch side that is not a power of two, or a window R below
+    the tensor's side (its top-left R x R pixels), goes through aph_patchify_f16_win: f16 rows of patch_row_elems(patch), zero pad columns"""
     L = _L(lib, x)
     _chk(x, torch.float32, 'x')
-    S, _, R, _ = x.shape
+    S, _, R_src, _ = x.shape
+    R = R_src if R is None else int(R)
     g = R // patch
+    if not _pow2(patch) or R != R_src:
+        if hilo or f32:
+            raise ValueError('patchify: patch %d / a window has f16 rows only (no hilo / f32 operand)' % patch)
+        out = torch.empty(S * g * g, patch_row_elems(patch), dtype=torch.float16, device=x.device)
+        L.call('aph_patchify_f16_win', ptr(x), S, R_src, R, patch, ptr(out), _stream(x))
+        return out
     if f32:
         out = torch.empty(S * g * g, 3 * patch * patch, dtype=torch.float32, device=x.device)
         L.call('aph_patchify_f32', ptr(x), S, R, patch, ptr(out), _stream(x))
@@ -207,11 +225,17 @@ def patchify(x, patch, lib=None, hilo=False, f32=False):
     return out
 
 
-def unpatchify(g, S, R, patch, gscale=1.0, lib=None):
+def unpatchify(g, S, R, patch, gscale=1.0, lib=None, R_src=None, out=None):
+    """the adjoint of patchify: patch-major f32 gradient -> [S,3,R_src,R_src] (R_src = R by default; zero outside the R x R window)"""
     L = _L(lib, g)
     _chk(g, torch.float32, 'g')
-    out = torch.empty(S, 3, R, R, dtype=torch.float32, device=g.device)
-    L.call('aph_unpatchify_f32', ptr(g), S, R, patch, float(gscale), ptr(out), _stream(g))
+    R_src = R if R_src is None else int(R_src)
+    if out is None:
+        out = torch.empty(S, 3, R_src, R_src, dtype=torch.float32, device=g.device)
+    if not _pow2(patch) or R != R_src:
+        L.call('aph_unpatchify_f32_win', ptr(g), S, R_src, R, patch, float(gscale), ptr(out), _stream(g))
+    else:
+        L.call('aph_unpatchify_f32', ptr(g), S, R, patch, float(gscale), ptr(out), _stream(g))
     return out
 
 
@@ -231,7 +255,8 @@ class VitHandle:
             a = np.ascontiguousarray(v.detach().cpu().float().numpy())
             self.lib.call('aph_vit_set_weight', self.handle, k.encode(), a.ctypes.data_as(c_void_p), a.size)
         g = cfg['input_resolution'] // cfg['patch_size']
-        self.P, self.T, self.Kp = g * g, g * g + 1, 3 * cfg['patch_size'] ** 2
+        self.P, self.T, self.Kp = g * g, g * g + 1, patch_row_elems(cfg['patch_size'])      # Kp: the padded row length
+        self.padded = self.Kp != 3 * cfg['patch_size'] ** 2
         self._hilo = False
         self._f32 = False
 

@@ -12,6 +12,7 @@ import torch
 VIT_CONFIGS = {
     'ViT-B/32': dict(input_resolution=224, patch_size=32, width=768, layers=12, heads=12, output_dim=512),
     'ViT-B/16': dict(input_resolution=224, patch_size=16, width=768, layers=12, heads=12, output_dim=512),
+    'ViT-L/14': dict(input_resolution=224, patch_size=14, width=1024, layers=24, heads=16, output_dim=768),
 }
 
 

@@ -26,7 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-clip_models = ['ViT-B/16', 'ViT-B/32', 'RN101', 'RN50x16', 'RN50x4', 'RN50']
+clip_models = ['ViT-B/16', 'ViT-B/32', 'ViT-L/14', 'RN101', 'RN50x16', 'RN50x4', 'RN50']
 
 
 def get_args(argv=None):
@@ -111,7 +111,7 @@ def get_args(argv=None):
 
 def derate_samples(a):
     """The reference's sample-count arithmetic, in its order (clip_fft.py:125-127,134,157-169,187,199)."""
-    xmem = {'ViT-B/16': 0.25, 'RN50': 0.5, 'RN50x4': 0.16, 'RN50x16': 0.06, 'RN101': 0.33}
+    xmem = {'ViT-B/16': 0.25, 'ViT-L/14': 0.04, 'RN50': 0.5, 'RN50x4': 0.16, 'RN50x16': 0.06, 'RN101': 0.33}      # (ViT-L/14: illustra.py:97, the same generator)
     s = a.samples
     if a.model in xmem:
         s = int(s * xmem[a.model])
@@ -251,7 +251,7 @@ def main(argv=None):
         torch.manual_seed(a.seed)
         np.random.seed(a.seed)
     if not a.model.startswith('ViT'):
-        raise SystemExit(' the MI355X path covers the ViT CLIP models (ViT-B/32, ViT-B/16); got %s' % a.model)
+        raise SystemExit(' the MI355X path covers the ViT CLIP models (ViT-B/32, ViT-B/16, ViT-L/14); got %s' % a.model)
     from aphantasia_amd import clip as aclip, transforms
     from aphantasia_amd.image import to_valid_rgb, fft_image, dwt_image
     from aphantasia_amd.utils import slice_imgs, sim_func, basename, img_list, img_read, txt_clean
@@ -343,8 +343,15 @@ def main(argv=None):
                              'sa_0_4_<model>_linear.pth from github.com/LAION-AI/aesthetic-predictor; there is no network here)')
         sd = torch.load(path, map_location='cpu')
         return (sd['weight'].float(), float(sd['bias'].reshape(-1)[0]), a.aest)
+
+    def check_aest(head, model, flag):                                                # utils.py:403: nf = 768 for ViT-L/14, 512 for ViT-B/*
+        if head is not None and head[0].numel() != model.visual.output_dim:
+            raise SystemExit(' %s: a head of %d inputs, but %s encodes into %d (sa_0_4_vit_l_14_linear.pth is the 768-wide one)'
+                             % (flag, head[0].numel(), model.name, model.visual.output_dim))
     aest1 = load_aest(a.aest_weights)
     aest2 = load_aest(a.aest_weights2) if a.dualmod is not None else None
+    check_aest(aest1, model_clip, '--aest-weights')
+    if a.dualmod is not None: check_aest(aest2, model_clip2, '--aest-weights2')
     h, w = a.size
     if a.dwt is True:
         pk = dict(param_kind='dwt', dwt=image_f.synth)

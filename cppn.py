@@ -8,6 +8,8 @@ snapshots).  Generator, sampler, ViT, loss and Adam run as one fused step (aphan
 
 Additive flags, with the meaning they have in clip_fft.py: --clip-weights[2], --aest-weights[2], --seed, --rng, --no_save, --no-graph, --exact.
 Refused with a message: -sh (the Sobel derivative is not built), -ex (shader export is not part of this path), the RN* and ViT-L/14 models, -tr.
+(The ViT-L/14 tower itself exists now -- aphantasia_amd.clip.load('ViT-L/14'), clip_fft.py -m ViT-L/14; admitting the flag here, with
+cppn.py:197's 0.11 derating, is the follow-up.)
 """
 import argparse
 import os

@@ -40,7 +40,7 @@ def get_args(argv=None):
     p.add_argument('-nv', '--no-verbose', dest='verbose', action='store_false')
     p.set_defaults(verbose=True)
     p.add_argument('--gen', default='RGB')
-    p.add_argument('-m', '--model', default='ViT-B/32', choices=['ViT-B/16', 'ViT-B/32'])
+    p.add_argument('-m', '--model', default='ViT-B/32', choices=['ViT-B/16', 'ViT-B/32', 'ViT-L/14'])
     p.add_argument('--steps', default=300, type=int, help='frames per scene')
     p.add_argument('--samples', default=100, type=int)
     p.add_argument('-lr', '--lrate', default=0.1, type=float)
@@ -98,7 +98,7 @@ def get_args(argv=None):
 
 def derate_samples(a):
     """illustrip.py:152-160,177-179"""
-    xmem = {'ViT-B/16': 0.25}
+    xmem = {'ViT-B/16': 0.25, 'ViT-L/14': 0.04}      # (ViT-L/14: illustra.py:97)
     s = a.samples
     if a.model in xmem: s = int(s * xmem[a.model])
     if a.dualmod is not None: s = int(s * 0.23)

@@ -212,6 +212,18 @@ int aph_patchify_f16_hilo(const float* d_nchw, int S, int R, int patch, void* d_
 /* the same in f32 (APH_OUT_PATCH_F32 layout, values unchanged): d_patches f32 [S*(R/patch)^2, 3*patch^2] */
 int aph_patchify_f32(const float* d_nchw, int S, int R, int patch, float* d_patches, void* stream);
 int aph_unpatchify_f32(const float* d_patch_grad, int S, int R, int patch, float gscale, float* d_nchw_grad, void* stream);
+/* Elements of one row of the patch-major operand: round_up(3*patch^2, 128) -- 3072 for patch 32, 768 for patch 16 (3*patch^2 itself: a
+ * multiple of 128 already), 640 for patch 14 (588 elements and 52 pad columns that are always zero: the patch-embedding GEMM needs
+ * K % 64 == 0 and its dgrad N % 128 == 0).  Padded rows exist only for patch sides that are no power of two (made by aph_patchify_f16_win);
+ * a power-of-two patch of 8 or less (3*patch^2 = 192 ...) has no padded form and aph_vit_create refuses it.  0 for patch < 1. */
+int aph_patch_row_elems(int patch);
+/* The same conversions for ANY patch side (the sampler's patch-major modes and the entries above need a power of two), with a window: reads the
+ * top-left R x R window of d_nchw f32 [S,3,R_src,R_src] and writes d_patches f16 [S*(R/patch)^2, aph_patch_row_elems(patch)], order
+ * k = (iy*patch + ix)*3 + c inside a row, the pad columns k >= 3*patch^2 written as zero on every call.  R_src >= R, R % patch == 0. */
+int aph_patchify_f16_win(const float* d_nchw, int S, int R_src, int R, int patch, void* d_patches, void* stream);
+/* its exact adjoint: d_patch_grad f32 [S*(R/patch)^2, aph_patch_row_elems(patch)] -> d_nchw_grad f32 [S,3,R_src,R_src] = gradient * gscale
+ * inside the window, 0 outside; every element is written, nothing is accumulated; the pad columns are not read. */
+int aph_unpatchify_f32_win(const float* d_patch_grad, int S, int R_src, int R, int patch, float gscale, float* d_nchw_grad, void* stream);
 
 /* ---- CLIP ViT visual tower: model.encode_image (clip_fft.py:254) + its input-gradient ----- */
 typedef struct aph_vit aph_vit;
@@ -223,7 +235,15 @@ int aph_vit_destroy(aph_vit* vit);
 size_t aph_vit_workspace_bytes(const aph_vit* vit);
 /* one tensor by its OpenAI checkpoint key without the "visual." prefix (fp32 HOST data) */
 int aph_vit_set_weight(aph_vit* vit, const char* name, const float* h_data, size_t count);
-/* d_patches f16 [S*P, 3*patch^2] (APH_OUT_PATCH_F16 layout) -> d_enc f32 [S, output_dim] */
+/* Shapes below: P = (input_resolution / patch)^2 patches per cut, Kp = aph_patch_row_elems(patch) elements per patch row.  Kp = 3*patch^2 for
+ * the power-of-two patches (ViT-B/32, ViT-B/16); for patch 14 (ViT-L/14) Kp = 640: rows of 588 elements and 52 zero pad columns, made by
+ * aph_patchify_f16_win.  aph_vit_set_weight zero-fills the pad columns of conv1.weight in W and W^T, so the patch embedding (K = Kp) ignores
+ * whatever the pad columns of its operand hold only if they are finite -- aph_patchify_f16_win writes zeros -- and the last dgrad GEMM
+ * (N = Kp) writes exact zeros into the pad columns of the gradient.
+ * Supported: width in {256, 512, 768, 1024} with head dim 64; a power-of-two patch with 3*patch^2 % 128 == 0 (16, 32, 64) and T = P + 1 <= 256
+ * tokens, as before; any patch <= 64 that is no power of two, T <= 320 (ViT-L/14: patch 14, 257 tokens).  The split-precision and exact paths
+ * (aph_vit_enable_hilo / aph_vit_enable_f32) are refused (APH_ERR_UNSUPPORTED) for T > 256 or a patch that is no power of two.
+ * d_patches f16 [S*P, Kp] (APH_OUT_PATCH_F16 layout) -> d_enc f32 [S, output_dim] */
 int aph_vit_forward(aph_vit* vit, const void* d_patches, int S, float* d_enc, void* stream);
 /* SPLIT-PRECISION forward (opt-in: clip_fft.py --precise, bench.py --split; the default is aph_vit_forward -- f16 operands everywhere, the
  * reference's own GPU dtype -- since round 6): d_patches_hilo f16 [S*P, 2 * 3*patch^2] (APH_OUT_PATCH_F16_HILO rows [hi | lo]).  The
@@ -248,9 +268,9 @@ int aph_vit_forward_f32(aph_vit* vit, const float* d_patches, int S, float* d_en
 /* input-gradient of the last aph_vit_forward_f32 (refused after any other forward; aph_vit_backward is refused after this forward):
  * d_genc f32 [S, output_dim] -> d_patch_grad f32 [S*P, 3*patch^2] x out_scale; fp32 gradient stream end to end */
 int aph_vit_backward_f32(aph_vit* vit, const float* d_genc, int S, float* d_patch_grad, float out_scale, void* stream);
-/* d_genc f32 [S, output_dim] (times the caller's loss scale) -> d_patch_grad f32 [S*P, 3*patch^2] times out_scale */
+/* d_genc f32 [S, output_dim] (times the caller's loss scale) -> d_patch_grad f32 [S*P, Kp] times out_scale (pad columns: exact zeros) */
 int aph_vit_backward(aph_vit* vit, const float* d_genc, int S, float* d_patch_grad, float out_scale, void* stream);
-/* same with the patch gradient stored as f16 (keep the loss scale in it: out_scale = 1, and undo it in aph_sample_bwd's
+/* same with the patch gradient stored as f16 [S*P, Kp] (keep the loss scale in it: out_scale = 1, and undo it in aph_sample_bwd's
  * gscale with out_mode APH_GRAD_PATCH_F16): halves the bytes the sampler adjoint gathers */
 int aph_vit_backward_h(aph_vit* vit, const float* d_genc, int S, void* d_patch_grad_f16, float out_scale, void* stream);
 /* (test / measurement hooks -- GEMM core alone, per-launch GEMM timing -- are declared in aphantasia_hip_test.h) */
