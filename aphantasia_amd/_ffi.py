@@ -65,6 +65,12 @@ _PROTOTYPES = {
     'aph_grid_warp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     'aph_attn_test': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'aph_attn_f32_test': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'aph_attn_causal_f32_test': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'aph_text_create': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    'aph_text_destroy': (c_int, [c_void_p]),
+    'aph_text_workspace_bytes': (c_size_t, [c_void_p]),
+    'aph_text_set_weight': (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
+    'aph_text_forward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'aph_frame_affine': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_void_p]),
     'aph_patchify_f16': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_patchify_f16_hilo': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -1,21 +1,29 @@
-"""CLIP image tower for the optimisation loop: the piece of `clip.load(...)` / `model.encode_image`
-that clip_fft.py:119,254 uses, running on the HIP ViT (csrc/vit.hip).
+"""CLIP for the optimisation loop: the pieces of `clip.load(...)`, `model.encode_image`, `model.encode_text` and `clip.tokenize`
+that clip_fft.py:119,254 uses, running on the HIP ViT (csrc/vit.hip) and the HIP text tower (csrc/text.hip).
 
     model, _ = load('ViT-B/32', weights='/path/ViT-B-32.pt')     # OpenAI checkpoint if you have one
     model, _ = load('ViT-B/32')                                  # seeded synthetic weights (benchmarks/tests)
     enc = model.encode_image(cuts)                               # [S,3,224,224] normalised -> [S,512], autograd-aware
+    txt = model.encode_text(tokenize(['a cat'], bpe_vocab='/path/bpe_simple_vocab_16e6.txt.gz'))      # int [n,77] -> f32 [n,512]
+    txt = text_embedding(model, 'a cat', bpe_vocab=...)          # what the CLIs call: one prompt -> [1,512]
 
-The text tower / tokenizer (encode_text, clip.tokenize) run once per prompt, off the hot path; they
-are taken from the `clip` package when it is importable together with a real checkpoint, otherwise
-text prompts are mapped to seeded synthetic target embeddings (loud warning).
+The text tower runs once per prompt, off the hot path, in fp32 (the kernels of the exact ViT path with a causal attention): no f16 mode.
+It and the tokenizer (tokenizer.py) are this project's own; the `clip` package is never imported.  The BPE vocabulary is the user's file,
+like the checkpoint.  A model without a checkpoint (synthetic weights) has no text tower: its prompts are mapped to seeded synthetic
+target embeddings.
 """
 import hashlib
+import os
 import warnings
 
 import torch
 
 from . import ops
-from .weights import load_openai_checkpoint, synthetic_visual_weights, visual_config
+from .tokenizer import Tokenizer
+from .weights import load_openai_checkpoint, synthetic_visual_weights, text_config, text_weights, visual_config
+
+BPE_VOCAB_NAME = 'bpe_simple_vocab_16e6.txt.gz'
+TEXT_MAX_BATCH = 16       # prompts per aph_text_forward launch (encode_text walks a longer list in chunks of it)
 
 LOSS_SCALE = 4096.0     # static scale of the fp16 backward chain (precision table)
 
@@ -87,19 +95,50 @@ class VisualTransformer:
 
 
 class CLIPModel:
-    def __init__(self, name, cfg, weights, full_state=None, max_batch=256, lib=None, exact=False):
+    def __init__(self, name, cfg, weights, full_state=None, max_batch=256, lib=None, exact=False, weights_path=None):
         self.name = name
+        self.lib = lib
         self.visual = VisualTransformer(cfg, weights, max_batch, lib=lib, exact=exact)
         self._full_state = full_state
         self.synthetic = full_state is None
+        self.weights_path = weights_path
+        self._text = None              # ops.TextHandle, built from _full_state on the first encode_text
+        self.text_cfg = None
 
     def encode_image(self, image):
         return self.visual(image)
 
-    def encode_text(self, text):
-        raise NotImplementedError(
-            'encode_text needs the OpenAI text tower + BPE vocabulary (the `clip` package and a real checkpoint); '
-            'use aphantasia_amd.clip.text_embedding(model, prompt), which falls back to a seeded synthetic embedding')
+    def _text_handle(self):
+        if self._text is None:
+            if self._full_state is None:
+                raise RuntimeError('encode_text needs a checkpoint with a text tower (load(name, weights=...)); this model has synthetic '
+                                   'visual weights only -- text_embedding(model, prompt) gives it a seeded synthetic target')
+            self.text_cfg = text_config(self._full_state)
+            self._text = ops.TextHandle(self.text_cfg, text_weights(self._full_state), TEXT_MAX_BATCH, lib=self.lib)
+        return self._text
+
+    def encode_text(self, tokens):
+        """int tokens [n, context_length] (tokenize's rows) -> f32 [n, output_dim] on the visual tower's device; no gradient"""
+        handle = self._text_handle()
+        cfg = self.text_cfg
+        tokens = torch.as_tensor(tokens)
+        if tokens.dim() != 2 or tokens.shape[1] != cfg['context_length'] or tokens.dtype.is_floating_point or tokens.dtype == torch.bool:
+            raise ValueError('encode_text expects integer tokens [n, %d], got %s %s' % (cfg['context_length'], tokens.dtype, tuple(tokens.shape)))
+        host = tokens.detach().cpu().to(torch.int64)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= cfg['vocab_size']):
+            raise ValueError('encode_text: token ids must lie in [0, %d); got %d .. %d' % (cfg['vocab_size'], int(host.min()), int(host.max())))
+        dev = 'cpu' if self.lib is not None else 'cuda'          # (lib: the host interpreter build of the tests)
+        ids = host.to(torch.int32).contiguous().to(dev)
+        out = torch.empty(ids.shape[0], cfg['output_dim'], dtype=torch.float32, device=dev)
+        for s in range(0, ids.shape[0], TEXT_MAX_BATCH):
+            handle.forward(ids[s:s + TEXT_MAX_BATCH], out=out[s:s + TEXT_MAX_BATCH])
+        return out
+
+    def release_text(self):
+        """frees the text tower's device arena (about 0.25 GB for the ViT-B models, 0.5 GB for ViT-L/14); a later encode_text rebuilds it"""
+        if self._text is not None:
+            self._text.close()
+            self._text = None
 
     def float(self):
         return self
@@ -134,29 +173,62 @@ def load(name='ViT-B/32', device='cuda', jit=False, weights=None, seed=1, max_ba
         want = visual_config(name)
         if (cfg['patch_size'], cfg['width'], cfg['layers']) != (want['patch_size'], want['width'], want['layers']):
             raise ValueError('%s does not hold a %s visual tower' % (weights, name))
-        return _report_arena(CLIPModel(name, cfg, vis, full, max_batch, exact=exact)), None
+        return _report_arena(CLIPModel(name, cfg, vis, full, max_batch, exact=exact, weights_path=weights)), None
     cfg = visual_config(name)
     warnings.warn('aphantasia_amd.clip.load(%r): no checkpoint given -> seeded SYNTHETIC weights (seed %d); '
                   'images will not be meaningful, use --clip-weights for real runs' % (name, seed))
     return _report_arena(CLIPModel(name, cfg, synthetic_visual_weights(cfg, seed), None, max_batch, exact=exact)), None
 
 
-def text_embedding(model, text, device='cuda'):
-    """Target embedding for a prompt ([1, output_dim], detached).  Real text tower when available,
-    else a deterministic synthetic vector derived from the prompt (so runs are reproducible)."""
+_tokenizers = {}
+
+
+def _tokenizer(bpe_vocab, vocab_size):
+    key = (os.path.abspath(bpe_vocab), int(vocab_size))
+    if key not in _tokenizers:
+        _tokenizers[key] = Tokenizer(bpe_vocab, vocab_size)
+    return _tokenizers[key]
+
+
+def tokenize(texts, context_length=77, truncate=False, bpe_vocab=None, vocab_size=49408):
+    """clip.tokenize: str or list of str -> int32 [n, context_length] (SOT, ids, EOT, zero padding).  bpe_vocab: the vocabulary file
+    (upstream's bpe_simple_vocab_16e6.txt.gz, its text, or a HuggingFace merges.txt); vocab_size: rows of the checkpoint's token embedding."""
+    if bpe_vocab is None:
+        raise RuntimeError('tokenize needs the BPE vocabulary: pass bpe_vocab=/path/%s (the CLIs: --bpe-vocab)' % BPE_VOCAB_NAME)
+    return _tokenizer(bpe_vocab, vocab_size).tokenize(texts, context_length, truncate)
+
+
+def _find_vocab(model, bpe_vocab):
+    if bpe_vocab is not None:
+        if not os.path.isfile(bpe_vocab):
+            raise RuntimeError('BPE vocabulary %s not found (%s of openai/CLIP, or a merges.txt)' % (bpe_vocab, BPE_VOCAB_NAME))
+        return bpe_vocab
+    beside = os.path.join(os.path.dirname(os.path.abspath(model.weights_path)), BPE_VOCAB_NAME) if model.weights_path else None
+    if beside is not None and os.path.isfile(beside):
+        return beside
+    raise RuntimeError('text prompts need the BPE vocabulary %s of openai/CLIP (clip/%s in its repository): put it beside the checkpoint%s '
+                       'or pass its path with --bpe-vocab (text_embedding(..., bpe_vocab=PATH))'
+                       % (BPE_VOCAB_NAME, BPE_VOCAB_NAME, ' (%s)' % os.path.dirname(os.path.abspath(model.weights_path)) if model.weights_path else ''))
+
+
+def text_embedding(model, text, device='cuda', bpe_vocab=None):
+    """Target embedding for a prompt ([1, output_dim], detached).  A model with a checkpoint: this project's tokenizer and text tower
+    (bpe_vocab, else bpe_simple_vocab_16e6.txt.gz beside the checkpoint).  A synthetic model: a deterministic vector derived from the
+    prompt (so runs are reproducible)."""
     if not model.synthetic:
         # a real checkpoint: the target must come from its text tower -- a random stand-in would silently optimise towards
         # nothing while the output still looks like a valid run
-        try:
-            import clip as openai_clip          # the reference's dependency (openai/CLIP); tokenizer + text tower
-        except ImportError as e:
-            raise RuntimeError('text prompts with a real CLIP checkpoint need the `clip` package (openai/CLIP: BPE vocabulary + text '
-                               'tower); it is not importable here.  Pass image prompts (-i) or install it.') from e
-        if getattr(model, '_text_model', None) is None:
-            import copy
-            model._text_model = openai_clip.model.build_model(copy.copy(model._full_state)).float().to(device).eval()
-        with torch.no_grad():
-            return model._text_model.encode_text(openai_clip.tokenize(text).to(device)).detach().clone().float()
+        path = _find_vocab(model, bpe_vocab)
+        cfg = text_config(model._full_state)
+        tokens = tokenize(text, cfg['context_length'], bpe_vocab=path, vocab_size=cfg['vocab_size'])
+        return model.encode_text(tokens).detach().clone().float()
     h = int.from_bytes(hashlib.sha256(text.encode()).digest()[:4], 'little')
     g = torch.Generator().manual_seed(h)
     return torch.randn(1, model.visual.output_dim, generator=g).to(device)
+
+
+def release_text(*models):
+    """the CLIs call this once their targets are built: frees every model's text arena"""
+    for m in models:
+        if m is not None:
+            m.release_text()

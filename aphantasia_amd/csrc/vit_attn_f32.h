@@ -6,7 +6,7 @@
 // atomics: every output element is one thread's fixed-order sum -- bitwise repeatable.
 // A workgroup (4 waves) takes one (cut, head) and a block of kAtfRows rows; the whole head's other two operands are held in LDS
 // (rows padded to 65 floats where lanes walk rows: conflict-free), at T = 256 about 150 KiB:
-//   forward      (query block): K, V, the block's Q rows      -> att, lse
+//   forward      (query block): K, V, the block's Q rows      -> att, lse      (causal variant: the text tower's, see the kernel)
 //   backward dQ  (query block): K, V, the block's Q / dO rows -> dQ, delta_i = sum_j P_ij dP_ij
 //   backward dKV (key block):   Q, dO, the block's K / V rows -> dK, dV   (reads lse and delta)
 // A wave works one row at a time: lane j holds the scores of keys j, j + 64, ... (<= 4); the row's probabilities go through a
@@ -35,7 +35,11 @@ __device__ __forceinline__ void atf_stage(const float* __restrict__ src, int ld,
   }
 }
 
-inline __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ att, float* __restrict__ lse,
+// CAUSAL (the text tower): query row i attends to the keys j <= i only.  The later keys never enter a score, the maximum, the sum or the
+// P.V loop -- they are not masked after the fact, they are not read -- and only the i0 + nq K / V rows the block's rows can see are staged.
+// The non-causal instantiation runs the same statements with T keys for every row.
+template <bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ att, float* __restrict__ lse,
                                                            int T, int heads) {
   APH_DYN_SMEM(smem);
   const int nb = (T + kAtfRows - 1) / kAtfRows;
@@ -47,21 +51,23 @@ inline __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* _
   float* Qs = Vs + T * 64;                              // [kAtfRows][64]
   float* Ps = Qs + kAtfRows * 64;                       // [4 waves][256]
   const float* base = qkv + (size_t)s * T * ld + h * 64;
-  atf_stage(base + D, ld, T, Ks, kAtfPad);
-  atf_stage(base + 2 * D, ld, T, Vs, 64);
+  const int ns = CAUSAL ? i0 + nq : T;                  // K / V rows staged
+  atf_stage(base + D, ld, ns, Ks, kAtfPad);
+  atf_stage(base + 2 * D, ld, ns, Vs, 64);
   atf_stage(base + (size_t)i0 * ld, ld, nq, Qs, 64);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* P = Ps + wave * 256;
   for (int r = wave; r < nq; r += 4) {
     const float* q = Qs + r * 64;
+    const int nk = CAUSAL ? i0 + r + 1 : T;             // keys of this row
     float sc[4];
     float mx = -INFINITY;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = lane + 64 * c;
       float a = 0.f;
-      if (j < T) {
+      if (j < nk) {
         const float* k = Ks + j * kAtfPad;
         for (int d = 0; d < 64; ++d) a = fmaf(q[d], k[d], a);
         mx = a > mx ? a : mx;
@@ -73,7 +79,7 @@ inline __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* _
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = lane + 64 * c;
-      if (j < T) {
+      if (j < nk) {
         const float p = expf((sc[c] - mx) * 0.125f);
         sc[c] = p;
         l += p;
@@ -84,11 +90,11 @@ inline __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* _
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int j = lane + 64 * c;
-      if (j < T) P[j] = sc[c] * il;
+      if (j < nk) P[j] = sc[c] * il;
     }
     wave_lds_fence();
     float o = 0.f;
-    for (int j = 0; j < T; ++j) o = fmaf(P[j], Vs[j * 64 + lane], o);
+    for (int j = 0; j < nk; ++j) o = fmaf(P[j], Vs[j * 64 + lane], o);
     const int i = i0 + r;
     att[((size_t)s * T + i) * D + h * 64 + lane] = o;
     if (lane == 0) lse[((size_t)s * heads + h) * T + i] = mx * 0.125f + logf(l);
@@ -212,10 +218,11 @@ inline __global__ __launch_bounds__(256) void attn_bwd_dkv_f32_kernel(const floa
   }
 }
 
-inline void launch_attn_fwd_f32(const float* qkv, float* att, float* lse, int S, int T, int heads, hipStream_t st) {
+template <bool CAUSAL = false>
+void launch_attn_fwd_f32(const float* qkv, float* att, float* lse, int S, int T, int heads, hipStream_t st) {
   const size_t smem = attn_f32_smem(T, 0);
-  APH_ALLOW_SMEM(attn_fwd_f32_kernel, smem);
-  APH_LAUNCH(attn_fwd_f32_kernel, dim3(S * heads * ((T + kAtfRows - 1) / kAtfRows)), dim3(256), smem, st, qkv, att, lse, T, heads);
+  APH_ALLOW_SMEM(attn_fwd_f32_kernel<CAUSAL>, smem);
+  APH_LAUNCH(attn_fwd_f32_kernel<CAUSAL>, dim3(S * heads * ((T + kAtfRows - 1) / kAtfRows)), dim3(256), smem, st, qkv, att, lse, T, heads);
 }
 inline void launch_attn_bwd_f32(const float* qkv, const float* datt, const float* lse, float* delta, float* dqkv, int S, int T, int heads,
                                 hipStream_t st) {

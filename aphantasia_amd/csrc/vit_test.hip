@@ -160,6 +160,15 @@ int aph_attn_f32_test(const float* d_qkv, float* d_att, float* d_lse, const floa
   APH_CATCH
 }
 
+// the text tower's causal instantiation of the fp32 attention forward alone
+int aph_attn_causal_f32_test(const float* d_qkv, float* d_att, float* d_lse, int S, int T, int heads, void* stream_) {
+  APH_TRY
+  if (!d_qkv || !d_att || !d_lse || S < 1 || T < 1 || T > 256 || heads < 1) return aph_fail(APH_ERR_ARG, "aph_attn_causal_f32_test: bad argument");
+  launch_attn_fwd_f32<true>(d_qkv, d_att, d_lse, S, T, heads, (hipStream_t)stream_);
+  return aph_check_launch("aph_attn_causal_f32_test");
+  APH_CATCH
+}
+
 // the exact path's GEMM (vit_gemm_f32.h) alone, one launch per epi_kind
 int aph_gemm_f32_test(const float* d_A, int lda, int a_rowP, const float* d_Bt, int ldb, int M, int N, int K, float* d_C, int ldc, const float* d_bias,
                       float* d_aux, int epi_kind, float* d_ws, size_t ws_floats, void* stream_) {

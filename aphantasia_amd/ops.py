@@ -321,6 +321,54 @@ class VitHandle:
             pass
 
 
+class TextHandle:
+    """aph_text: the CLIP text tower's fp32 weights and the activations of `max_batch` prompts in one device arena.
+    cfg: context_length, vocab_size, width, layers, heads, output_dim (weights.text_config); weights: OpenAI top-level keys."""
+
+    def __init__(self, cfg, weights, max_batch, lib=None):
+        self.lib = lib if lib is not None else _ffi.lib()
+        self.cfg = dict(cfg)
+        self.max_batch = int(max_batch)
+        h = c_void_p()
+        self.lib.call('aph_text_create', cfg['context_length'], cfg['vocab_size'], cfg['width'], cfg['layers'], cfg['heads'], cfg['output_dim'],
+                      self.max_batch, byref(h))
+        self.handle = h
+        for k, v in weights.items():
+            a = np.ascontiguousarray(v.detach().cpu().float().numpy())
+            self.lib.call('aph_text_set_weight', self.handle, k.encode(), a.ctypes.data_as(c_void_p), a.size)
+
+    def workspace_bytes(self):
+        return int(self.lib.cdll.aph_text_workspace_bytes(self.handle))
+
+    def forward(self, tokens, out=None):
+        """tokens int32 [S, context_length] on the library's device -> f32 [S, output_dim] (aph_text_forward; ids are used as given -- the
+        kernel clamps them -- so callers validate first: CLIPModel.encode_text)"""
+        _chk(tokens, torch.int32, 'tokens')
+        if tokens.dim() != 2 or tokens.shape[1] != self.cfg['context_length']:
+            raise ValueError('TextHandle.forward: tokens %s, expected [S, %d]' % (tuple(tokens.shape), self.cfg['context_length']))
+        S = tokens.shape[0]
+        if out is None:
+            out = torch.empty(S, self.cfg['output_dim'], dtype=torch.float32, device=tokens.device)
+        self.lib.call('aph_text_forward', self.handle, ptr(tokens), int(S), ptr(out), _stream(tokens))
+        return out
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.cdll.aph_text_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def attn_causal_f32(qkv, att, lse, S, T, heads, lib=None):
+    """aph_attn_causal_f32_test: the text tower's causal fp32 attention forward alone (qkv [S T, 3 D] -> att [S T, D], lse [S heads T])"""
+    _L(lib, qkv).call('aph_attn_causal_f32_test', ptr(qkv), ptr(att), ptr(lse), int(S), int(T), int(heads), _stream(qkv))
+
+
 def gemm_f16(A, Bt, lib=None, tile_cfg=0):
     """C = A @ Bt^T (f16 in, f32 out); tile_cfg as in include/aphantasia_hip_test.h: 0 auto, 1 = 64x64, 2 = 256x128,
     8 / 9 = 64x64 split-K x2 / x4, 10 = 128x128, 22 / 24 = 128x128 split-K x2 / x4"""

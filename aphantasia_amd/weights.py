@@ -75,6 +75,59 @@ def f16_representable(w):
     return {k: v.half().float() for k, v in w.items()}
 
 
+TEXT_PREFIXES = ('token_embedding.', 'positional_embedding', 'ln_final.', 'text_projection', 'transformer.resblocks.')
+
+
+def text_weights(full_state):
+    """the text tower's tensors of a full OpenAI state dict (its top-level keys), fp32"""
+    return {k: v.float() for k, v in full_state.items() if k.startswith(TEXT_PREFIXES)}
+
+
+def text_config(full_state):
+    """context length, vocabulary size, width, layers, heads (= width // 64) and output_dim of the text tower, read off the state dict the
+    way clip.model.build_model does"""
+    for k in ('token_embedding.weight', 'positional_embedding', 'text_projection', 'ln_final.weight'):
+        if k not in full_state:
+            raise ValueError('the checkpoint holds no text tower (no %s)' % k)
+    vocab, width = full_state['token_embedding.weight'].shape
+    layers = len({k.split('.')[2] for k in full_state if k.startswith('transformer.resblocks.')})
+    return dict(context_length=full_state['positional_embedding'].shape[0], vocab_size=vocab, width=width, layers=layers,
+                heads=width // 64, output_dim=full_state['text_projection'].shape[1])
+
+
+def synthetic_text_weights(cfg, seed=1):
+    """Random text-tower weights following openai/CLIP's CLIP.initialize_parameters (token embedding std 0.02, positional 0.01, in_proj
+    width**-0.5, out_proj and c_proj width**-0.5 * (2 layers)**-0.5, c_fc (2 width)**-0.5, text_projection width**-0.5; LayerNorm unit gain;
+    biases zero, nn.Linear / MHA defaults aside).  fp32 at f16-representable values, OpenAI top-level keys."""
+    g = torch.Generator().manual_seed(seed)
+    width, layers = cfg['width'], cfg['layers']
+    attn_std, proj_std, fc_std = width ** -0.5, width ** -0.5 * (2 * layers) ** -0.5, (2 * width) ** -0.5
+
+    def randn(std, *s):
+        return std * torch.randn(*s, generator=g)
+
+    w = {'token_embedding.weight': randn(0.02, cfg['vocab_size'], width),
+         'positional_embedding': randn(0.01, cfg['context_length'], width)}
+    for i in range(layers):
+        pre = 'transformer.resblocks.%d.' % i
+        w[pre + 'attn.in_proj_weight'] = randn(attn_std, 3 * width, width)
+        w[pre + 'attn.in_proj_bias'] = torch.zeros(3 * width)
+        w[pre + 'attn.out_proj.weight'] = randn(proj_std, width, width)
+        w[pre + 'attn.out_proj.bias'] = torch.zeros(width)
+        w[pre + 'ln_1.weight'] = torch.ones(width)
+        w[pre + 'ln_1.bias'] = torch.zeros(width)
+        w[pre + 'mlp.c_fc.weight'] = randn(fc_std, 4 * width, width)
+        w[pre + 'mlp.c_fc.bias'] = randn(fc_std, 4 * width)
+        w[pre + 'mlp.c_proj.weight'] = randn(proj_std, width, 4 * width)
+        w[pre + 'mlp.c_proj.bias'] = randn(proj_std, width)
+        w[pre + 'ln_2.weight'] = torch.ones(width)
+        w[pre + 'ln_2.bias'] = torch.zeros(width)
+    w['ln_final.weight'] = torch.ones(width)
+    w['ln_final.bias'] = torch.zeros(width)
+    w['text_projection'] = randn(attn_std, width, cfg['output_dim'])
+    return f16_representable(w)
+
+
 def load_openai_checkpoint(path):
     """Reads an OpenAI CLIP archive (`ViT-B-32.pt`, TorchScript) or a plain state-dict
     file and returns (visual weights fp32 in the layout above, cfg, full state dict)."""

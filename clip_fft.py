@@ -74,6 +74,7 @@ def get_args(argv=None):
     # additive (not in the reference)
     parser.add_argument(       '--clip-weights', dest='clip_weights', default=None, help='OpenAI CLIP checkpoint (ViT-B-32.pt); second model: --clip-weights2')
     parser.add_argument(       '--clip-weights2', dest='clip_weights2', default=None, help='checkpoint of the --dualmod model (ViT-B-16.pt)')
+    parser.add_argument(       '--bpe-vocab', dest='bpe_vocab', default=None, help='BPE vocabulary of the text prompts (bpe_simple_vocab_16e6.txt.gz; default: beside the checkpoint)')
     parser.add_argument(       '--seed',    default=None, type=int, help='seed torch/numpy RNG (reference: unseeded)')
     parser.add_argument(       '--no_save', action='store_true', help='do not write the per-step JPEG frames')
     parser.add_argument(       '--precise', action='store_true', help='opt-in split-precision ViT forward (patch-embedding and QKV GEMMs on hi + lo f16 activation pairs): ~5 %% slower, lower single-step gradient error; '
@@ -293,7 +294,7 @@ def main(argv=None):
                 [subtxt, wt] = subtxt.split(':')
                 wt = float(wt)
             else: wt = 1.
-            embs.append([aclip.text_embedding(model, subtxt), wt])
+            embs.append([aclip.text_embedding(model, subtxt, bpe_vocab=a.bpe_vocab), wt])
         return embs
 
     trform_f = pick_transform(a.transform)
@@ -325,6 +326,7 @@ def main(argv=None):
                 targets2.append((model_clip2.encode_image(in_sliced).detach().clone(), sign * a.weight_img))
         out_name.append(basename(a.in_img).replace(' ', '_'))
     assert targets, ' Loss not defined, check the inputs'                              # clip_fft.py:286
+    aclip.release_text(model_clip, model_clip2 if a.dualmod is not None else None)     # the targets are built: the text arenas can go
 
     if a.verbose is True: print(' samples:', a.samples)
     out_name = '-'.join(out_name)

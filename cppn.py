@@ -59,6 +59,7 @@ def get_args(argv=None):
     # additive (not in the reference; as in clip_fft.py)
     parser.add_argument(       '--clip-weights', dest='clip_weights', default=None, help='OpenAI CLIP checkpoint (ViT-B-32.pt); second model: --clip-weights2')
     parser.add_argument(       '--clip-weights2', dest='clip_weights2', default=None, help='checkpoint of the --dualmod model (ViT-B-16.pt)')
+    parser.add_argument(       '--bpe-vocab', dest='bpe_vocab', default=None, help='BPE vocabulary of the text prompts (bpe_simple_vocab_16e6.txt.gz; default: beside the checkpoint)')
     parser.add_argument(       '--aest-weights', dest='aest_weights', default=None, help='state dict of the LAION aesthetic head of the model')
     parser.add_argument(       '--aest-weights2', dest='aest_weights2', default=None, help='the head of the --dualmod model')
     parser.add_argument(       '--seed',    default=None, type=int, help='seed torch/numpy RNG (reference: unseeded); the network then starts from the reference\'s weights')
@@ -149,11 +150,11 @@ def main(argv=None):
     out_name = []
     if a.in_txt is not None:
         print(' ref text: ', basename(a.in_txt))
-        for t, m in zip(targets, models): t.append((aclip.text_embedding(m, a.in_txt), -1.0))
+        for t, m in zip(targets, models): t.append((aclip.text_embedding(m, a.in_txt, bpe_vocab=a.bpe_vocab), -1.0))
         out_name.append(txt_clean(a.in_txt))
     if a.in_txt0 is not None:
         print(' no text: ', basename(a.in_txt0))
-        for t, m in zip(targets, models): t.append((aclip.text_embedding(m, a.in_txt0), 0.5))
+        for t, m in zip(targets, models): t.append((aclip.text_embedding(m, a.in_txt0, bpe_vocab=a.bpe_vocab), 0.5))
     if a.in_img is not None and os.path.isfile(a.in_img):
         print(' ref image:', basename(a.in_img))
         img_in = torch.from_numpy(img_read(a.in_img) / 255.).unsqueeze(0).permute(0, 3, 1, 2).cuda().float()[:, :3]
@@ -163,6 +164,7 @@ def main(argv=None):
         out_name.append(basename(a.in_img).replace(' ', '_'))
     if not targets[0]:
         raise SystemExit(' Loss not defined, check the inputs (-t, -t0, -i)')
+    aclip.release_text(*models)                                                      # the targets are built: the text arenas can go
 
     sfx = '-l%d-n%d' % (a.layers, a.nf)                                              # cppn.py:259-265
     if a.dualmod is not None: sfx += '-dm%d' % a.dualmod

@@ -71,6 +71,7 @@ def get_args(argv=None):
     # additive
     p.add_argument('--clip-weights', dest='clip_weights', default=None)
     p.add_argument('--clip-weights2', dest='clip_weights2', default=None)
+    p.add_argument('--bpe-vocab', dest='bpe_vocab', default=None, help='BPE vocabulary of the text prompts (bpe_simple_vocab_16e6.txt.gz; default: beside the checkpoint)')
     p.add_argument('--seed', default=None, type=int)
     p.add_argument('--no_save', action='store_true')
     p.add_argument('--rng', default=None, choices=['bulk', 'reference'])
@@ -170,7 +171,8 @@ def main(argv=None):
             for sub in txt.split('|'):
                 wt = 1.
                 if ':' in sub: sub, wt = sub.split(':')[0], float(sub.split(':')[1])
-                out.append((aclip.text_embedding(m, sub), sign * wt))
+                out.append((aclip.text_embedding(m, sub, bpe_vocab=a.bpe_vocab), sign * wt))
+        m.release_text()          # the targets are built: the text arena can go
         return out
     trf = clip_fft.pick_transform(a.transform)
     if a.gen == 'RGB':                                                                          # illustrip.py:270-272: pixel_image([1,3,*size], resume) -> randn * sd, sd = 1 (image.py:98-101)

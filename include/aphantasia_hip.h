@@ -275,6 +275,27 @@ int aph_vit_backward(aph_vit* vit, const float* d_genc, int S, float* d_patch_gr
 int aph_vit_backward_h(aph_vit* vit, const float* d_genc, int S, void* d_patch_grad_f16, float out_scale, void* stream);
 /* (test / measurement hooks -- GEMM core alone, per-launch GEMM timing -- are declared in aphantasia_hip_test.h) */
 
+/* ---- CLIP text tower: clip_fft.py:119 `model.encode_text(clip.tokenize(text))`, forward only (a prompt is a constant) ----
+ * mirrors the text half of clip.model.CLIP: context_length tokens, vocab_size embeddings, `layers` residual blocks of `width` (causal
+ * attention, head dim 64), ln_final and text_projection [width, output_dim].  fp32 throughout -- the kernels of the exact ViT path
+ * (f32-input MFMA GEMM, fp32 LayerNorm, fp32 attention in its causal form): the result differs from an fp32 CPU evaluation in summation
+ * order only, and a prompt's embedding does not depend on the other prompts of its batch.  One arena holds the fp32 weights [N, K] and
+ * the activations of max_batch prompts; it is sized at create and aph_text_forward allocates nothing.
+ * Refused: width != 64 * heads, width no multiple of 256 or above 1024, context_length > 256 (APH_ERR_UNSUPPORTED); S outside 1 .. max_batch,
+ * a forward before every tensor is loaded, an unknown key or a wrong element count (APH_ERR_ARG). */
+typedef struct aph_text aph_text;
+int aph_text_create(int context_length, int vocab_size, int width, int layers, int heads, int output_dim, int max_batch, aph_text** out);
+int aph_text_destroy(aph_text* text);
+size_t aph_text_workspace_bytes(const aph_text* text);
+/* one tensor by its OpenAI checkpoint key (fp32 HOST data, the checkpoint's layout): token_embedding.weight, positional_embedding,
+ * ln_final.{weight,bias}, text_projection, transformer.resblocks.N.{ln_1,ln_2}.{weight,bias},
+ * transformer.resblocks.N.attn.{in_proj_weight,in_proj_bias,out_proj.weight,out_proj.bias}, transformer.resblocks.N.mlp.{c_fc,c_proj}.{weight,bias} */
+int aph_text_set_weight(aph_text* text, const char* name, const float* h_data, size_t count);
+/* d_tokens int32 [S, context_length] (device; clip.tokenize rows: SOT, ids, EOT, zero padding) -> d_enc f32 [S, output_dim]: row s is
+ * ln_final of the token row at the first position of the largest id of sequence s (upstream's text.argmax(dim=-1)) times text_projection.
+ * Ids are clamped into [0, vocab_size) on the device, so no id reads out of bounds; callers should refuse them earlier. */
+int aph_text_forward(aph_text* text, const int32_t* d_tokens, int S, float* d_enc, void* stream);
+
 /* ---- loss: aphantasia/utils.py:270-295 sim_func, assembled as at clip_fft.py:257-267 -------- */
 #define APH_SIM_COS 0   /* type None / 'cossim' */
 #define APH_SIM_MIX 1   /* 'mix' (default) */

@@ -27,6 +27,9 @@ int aph_attn_test(const void* d_qkv, void* d_att, float* d_lse, const void* d_da
  * mode, and in mode 1 a NULL d_datt, d_delta or d_dqkv. */
 int aph_attn_f32_test(const float* d_qkv, float* d_att, float* d_lse, const float* d_datt, float* d_delta, float* d_dqkv, int S, int T, int heads,
                       int mode, void* stream);
+/* The text tower's causal instantiation of the fp32 attention forward alone: as aph_attn_f32_test mode 0, but query row i sees the keys j <= i
+ * only (the later keys are not read into a score at all).  Refused (APH_ERR_ARG): a NULL buffer, S, T, heads < 1, T > 256. */
+int aph_attn_causal_f32_test(const float* d_qkv, float* d_att, float* d_lse, int S, int T, int heads, void* stream);
 /* the exact path's f32-input MFMA GEMM alone: C = epilogue(A * Bt^T), f32 in / out.  epi_kind 0 = plain (pitch ldc), 1 = + bias, 2 = QuickGELU
  * (C = g, d_aux = dg/du), 3 = GELU backward (C = acc * d_aux), 4 = residual (C = d_aux + acc + bias).  d_ws (ws_floats): split-K workspace or
  * NULL (never split).  a_rowP > 0: A row m is read from row m + m / a_rowP + 1 (the patch rows of a token-major buffer). */
