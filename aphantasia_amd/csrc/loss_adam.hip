@@ -138,7 +138,6 @@ __global__ void loss_reduce_kernel(const float* __restrict__ partial, int S, flo
 // Adam / AdamW (torch.optim semantics, single tensor).  hyper = device floats so a captured graph
 // can be replayed with new step / lr:  {lr, beta1, beta2, eps, weight_decay, bias_corr1, sqrt(bias_corr2), gradscale}
 // ---------------------------------------------------------------------------------
-// guard[0] = running count of skipped (overflowed) steps, guard[1] = "this step's gradient has a non-finite element"
 // Linear head on the encodings -- the aesthetic predictor of clip_fft.py:255-256 / utils.py:402-413
 // (`loss -= 0.001 * a.aest * aest(out_enc).mean()`, aest = nn.Linear(D, 1)):
 //   loss += coef * ( sum_s (w . enc_s + bias) ) / denom ,   genc[s][d] += gscale * coef * w[d] / denom
@@ -187,6 +186,7 @@ __global__ void rgb_to_u8_kernel(const float* __restrict__ rgb, unsigned char* _
   }
 }
 
+// guard[0] = running count of skipped (overflowed) steps, guard[1] = "this step's gradient has a non-finite element"
 // (the gradient as 16-byte quads when its base is 16-byte aligned -- one quad per thread, every load of the launch in flight at
 // once; the scalar loop this replaces made ten dependent round trips per thread: 7.4 us for 11 MB)
 template <bool VEC>

@@ -7,6 +7,7 @@
 
 #include "aph_device.h"
 #include "aph_host.h"
+#include "tower_store.h"
 #include "vit_gemm.h"
 #include "vit_ops.h"
 #include "vit_gemm_f32.h"
@@ -79,12 +80,6 @@ struct TextLayer {
   float *b_qkv = nullptr, *b_o = nullptr, *b_fc1 = nullptr, *b_fc2 = nullptr;
   float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
 };
-struct TextWeight {
-  std::string key;            // OpenAI checkpoint key (top level: the text tower has no prefix)
-  size_t count;
-  float** dst;
-  bool set = false;
-};
 
 }  // namespace
 
@@ -93,7 +88,7 @@ struct aph_text {
   float *tok = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *proj = nullptr;
   std::vector<TextLayer> layers;
   float *x = nullptr, *x_mid = nullptr, *h = nullptr, *qkv = nullptr, *att = nullptr, *g = nullptr, *lse = nullptr;      // activations of one forward
-  std::vector<TextWeight> weights;
+  std::vector<Weight> weights;         // every checkpoint tensor (tower_store.h): fp32 entries, keys at the checkpoint's top level (no prefix)
   char* arena = nullptr;
   size_t arena_bytes = 0;
 };
@@ -102,37 +97,32 @@ namespace {
 
 void text_build_weights(aph_text* v) {
   const size_t D = v->D;
-  auto add = [&](std::string key, size_t count, float** dst) { v->weights.push_back(TextWeight{std::move(key), count, dst}); };
-  add("token_embedding.weight", (size_t)v->vocab * D, &v->tok);
-  add("positional_embedding", (size_t)v->ctx * D, &v->pos);
-  add("ln_final.weight", D, &v->lnf_g); add("ln_final.bias", D, &v->lnf_b);
-  add("text_projection", D * v->E, &v->proj);
+  std::vector<Weight>& t = v->weights;
+  add_f32(t, "token_embedding.weight", v->vocab, D, &v->tok);
+  add_f32(t, "positional_embedding", v->ctx, D, &v->pos);
+  add_f32(t, "ln_final.weight", 1, D, &v->lnf_g); add_f32(t, "ln_final.bias", 1, D, &v->lnf_b);
+  add_f32(t, "text_projection", D, v->E, &v->proj);
   for (int li = 0; li < v->L; ++li) {
     TextLayer& l = v->layers[li];
     const std::string p = "transformer.resblocks." + std::to_string(li) + ".";
-    add(p + "attn.in_proj_weight", 3 * D * D, &l.w_qkv); add(p + "attn.in_proj_bias", 3 * D, &l.b_qkv);
-    add(p + "attn.out_proj.weight", D * D, &l.w_o); add(p + "attn.out_proj.bias", D, &l.b_o);
-    add(p + "mlp.c_fc.weight", 4 * D * D, &l.w_fc1); add(p + "mlp.c_fc.bias", 4 * D, &l.b_fc1);
-    add(p + "mlp.c_proj.weight", 4 * D * D, &l.w_fc2); add(p + "mlp.c_proj.bias", D, &l.b_fc2);
-    add(p + "ln_1.weight", D, &l.ln1_g); add(p + "ln_1.bias", D, &l.ln1_b);
-    add(p + "ln_2.weight", D, &l.ln2_g); add(p + "ln_2.bias", D, &l.ln2_b);
+    add_f32(t, p + "attn.in_proj_weight", 3 * D, D, &l.w_qkv); add_f32(t, p + "attn.in_proj_bias", 1, 3 * D, &l.b_qkv);
+    add_f32(t, p + "attn.out_proj.weight", D, D, &l.w_o); add_f32(t, p + "attn.out_proj.bias", 1, D, &l.b_o);
+    add_f32(t, p + "mlp.c_fc.weight", 4 * D, D, &l.w_fc1); add_f32(t, p + "mlp.c_fc.bias", 1, 4 * D, &l.b_fc1);
+    add_f32(t, p + "mlp.c_proj.weight", D, 4 * D, &l.w_fc2); add_f32(t, p + "mlp.c_proj.bias", 1, D, &l.b_fc2);
+    add_f32(t, p + "ln_1.weight", 1, D, &l.ln1_g); add_f32(t, p + "ln_1.bias", 1, D, &l.ln1_b);
+    add_f32(t, p + "ln_2.weight", 1, D, &l.ln2_g); add_f32(t, p + "ln_2.bias", 1, D, &l.ln2_b);
   }
 }
 
-// every weight in table order, then the activations of max_batch prompts; base == nullptr: sizes only
+// every weight in table order, then the activations of max_batch prompts; returns the size (base == nullptr: null pointers, the size alone)
 size_t text_carve(aph_text* v, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += (n * sizeof(float) + 255) & ~(size_t)255;
-    return p;
-  };
-  for (TextWeight& w : v->weights) *w.dst = take(w.count);
+  Carver c{base};
+  carve_weights(v->weights, c, 0, v->weights.size(), ARENA_MAIN);
   const size_t D = v->D, Mx = (size_t)v->max_batch * v->ctx;
-  v->x = take(Mx * D); v->x_mid = take(Mx * D); v->h = take(Mx * D);
-  v->qkv = take(Mx * 3 * D); v->att = take(Mx * D); v->g = take(Mx * 4 * D);
-  v->lse = take((size_t)v->max_batch * v->heads * v->ctx);
-  return off;
+  v->x = c.take<float>(Mx * D); v->x_mid = c.take<float>(Mx * D); v->h = c.take<float>(Mx * D);
+  v->qkv = c.take<float>(Mx * 3 * D); v->att = c.take<float>(Mx * D); v->g = c.take<float>(Mx * 4 * D);
+  v->lse = c.take<float>((size_t)v->max_batch * v->heads * v->ctx);
+  return c.off;
 }
 
 }  // namespace
@@ -156,11 +146,7 @@ int aph_text_create(int context_length, int vocab_size, int width, int layers, i
   v->ctx = context_length; v->vocab = vocab_size; v->D = width; v->L = layers; v->heads = heads; v->E = output_dim; v->max_batch = max_batch;
   v->layers.resize(layers);
   text_build_weights(v);
-  const size_t total = text_carve(v, nullptr);
-  const hipError_t me = hipMalloc((void**)&v->arena, total);
-  if (me != hipSuccess) { delete v; return aph_fail(APH_ERR_HIP, "aph_text_create: cannot allocate %zu bytes (%s)", total, hipGetErrorString(me)); }
-  v->arena_bytes = total;
-  text_carve(v, v->arena);
+  if (const int rc = alloc_arena("aph_text_create", &v->arena, &v->arena_bytes, [&](char* base) { return text_carve(v, base); })) { delete v; return rc; }
   *out = v;
   return APH_OK;
   APH_CATCH
@@ -179,13 +165,10 @@ size_t aph_text_workspace_bytes(const aph_text* v) { return v ? v->arena_bytes :
 int aph_text_set_weight(aph_text* v, const char* name, const float* data, size_t count) {
   APH_TRY
   if (!v || !name || !data) return aph_fail(APH_ERR_ARG, "aph_text_set_weight: null argument");
-  TextWeight* w = nullptr;
-  for (TextWeight& e : v->weights)
-    if (e.key == name) { w = &e; break; }
+  Weight* w = find_weight(v->weights, name);
   if (!w) return aph_fail(APH_ERR_ARG, "aph_text_set_weight: unknown key %s", name);
-  if (count != w->count) return aph_fail(APH_ERR_ARG, "aph_text_set_weight(%s): %zu elements, expected %zu", name, count, w->count);
-  if (hipMemcpy(*w->dst, data, count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-    return aph_fail(APH_ERR_HIP, "aph_text_set_weight(%s): upload failed", name);
+  if (count != w->rows * w->cols) return aph_fail(APH_ERR_ARG, "aph_text_set_weight(%s): %zu elements, expected %zu", name, count, w->rows * w->cols);
+  if (upload_f32(*w->f32[0], data, w->rows, w->cols, false)) return aph_fail(APH_ERR_HIP, "aph_text_set_weight(%s): upload failed", name);
   w->set = true;
   return APH_OK;
   APH_CATCH
@@ -196,11 +179,7 @@ int aph_text_set_weight(aph_text* v, const char* name, const float* data, size_t
 // the same for any S.
 int aph_text_forward(aph_text* v, const int32_t* d_tokens, int S, float* d_enc, void* stream_) {
   APH_TRY
-  if (!v || !d_tokens || !d_enc) return aph_fail(APH_ERR_ARG, "aph_text_forward: null argument");
-  if (S < 1 || S > v->max_batch) return aph_fail(APH_ERR_ARG, "aph_text_forward: batch %d outside 1..%d", S, v->max_batch);
-  int n = 0;
-  for (const TextWeight& w : v->weights) n += w.set;
-  if (n != (int)v->weights.size()) return aph_fail(APH_ERR_ARG, "aph_text_forward: weights not fully loaded (%d of %zu tensors)", n, v->weights.size());
+  if (const int rc = check_call(v, d_tokens, d_enc, S, "aph_text_forward")) return rc;
   hipStream_t st = (hipStream_t)stream_;
   const int D = v->D, T = v->ctx, M = S * T, nv = D / 256;
   const size_t n4 = (size_t)M * (D / 4);
@@ -208,11 +187,11 @@ int aph_text_forward(aph_text* v, const int32_t* d_tokens, int S, float* d_enc, 
              v->vocab, D);
   for (int li = 0; li < v->L; ++li) {
     const TextLayer& l = v->layers[li];
-    launch_ln_fwd<false, false>(nv, v->x, l.ln1_g, l.ln1_b, v->h, M, T, nullptr, nullptr, nullptr, st);
+    launch_ln_fwd<false, false>(nv, {.x = v->x, .g = l.ln1_g, .b = l.ln1_b, .out = v->h, .M = M, .T = T}, st);
     launch_gemm_f32(v->h, D, l.w_qkv, D, M, 3 * D, D, EpiBiasF32{v->qkv, 3 * D, l.b_qkv}, st, nullptr);
     launch_attn_fwd_f32<true>(v->qkv, v->att, v->lse, S, T, v->heads, st);
     launch_gemm_f32(v->att, D, l.w_o, D, M, D, D, EpiResidual{v->x_mid, v->x, D, l.b_o}, st, nullptr);
-    launch_ln_fwd<false, false>(nv, v->x_mid, l.ln2_g, l.ln2_b, v->h, M, T, nullptr, nullptr, nullptr, st);
+    launch_ln_fwd<false, false>(nv, {.x = v->x_mid, .g = l.ln2_g, .b = l.ln2_b, .out = v->h, .M = M, .T = T}, st);
     launch_gemm_f32(v->h, D, l.w_fc1, D, M, 4 * D, D, EpiGeluFwdF32{v->g, 4 * D, l.b_fc1}, st, nullptr);
     launch_gemm_f32(v->g, 4 * D, l.w_fc2, 4 * D, M, D, 4 * D, EpiResidual{v->x, v->x_mid, D, l.b_fc2}, st, nullptr);
   }

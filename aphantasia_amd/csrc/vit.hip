@@ -9,6 +9,7 @@
 
 #include "aph_device.h"
 #include "aph_host.h"
+#include "tower_store.h"
 #include "vit_gemm.h"
 #include "vit_gemm_ws.h"
 #include "vit_gemm_rs.h"
@@ -36,20 +37,6 @@ struct Layer {
   float *qkv32 = nullptr, *dg32 = nullptr;
 };
 
-// One checkpoint tensor and every device copy of it; the pointers name the members of aph_vit / Layer that the carve functions fill.
-// An f16 matrix [rows, cols] has h16 (the copy and its transpose, main arena), m32 (the fp32 copy and its transpose, the exact path's arena),
-// optionally rep (the copy repeated along K, hilo arena), and keeps its fp32 data in `host`, from which the enable calls fill rep and m32.
-// An fp32 tensor has f32 (the copy and, for `proj` alone, its transpose, main arena).  Absent copies are null.
-struct Weight {
-  std::string key;                     // OpenAI checkpoint key without the `visual.` prefix
-  size_t rows, cols;
-  half_t** h16[2];
-  half_t** rep;
-  float** m32[2];
-  float** f32[2];
-  std::vector<float> host;             // (conv1.weight in the sampler's K order)
-  bool set = false;                    // uploaded at least once
-};
 constexpr size_t kGlobalWeights = 8, kLayerWeights = 12;      // table order = carve order: the global tensors, then layer by layer
 
 }  // namespace
@@ -75,7 +62,7 @@ struct aph_vit {
   float *w_patch32 = nullptr, *w_patchT32 = nullptr;
   float *h32 = nullptr, *g32 = nullptr, *att32 = nullptr, *datt32 = nullptr, *dqkv32 = nullptr, *delta32 = nullptr;
   F32Space f32sp;                      // split-K partials of the fp32 class-row GEMMs
-  std::vector<Weight> weights;         // every checkpoint tensor (build_weights), looked up by key
+  std::vector<Weight> weights;         // every checkpoint tensor (build_weights; tower_store.h), looked up by key
   int last_fwd = 0;                    // precision of the last forward: 0 none, 1 f16 (aph_vit_forward / _hilo), 2 fp32 (aph_vit_forward_f32)
   // optional per-launch timing of the GEMM family (bench.py roofline): HIP event pairs on the launch stream
   bool prof_on = false;
@@ -86,79 +73,52 @@ struct aph_vit {
 
 namespace {
 
-struct Carver {
-  char* base; size_t off = 0;
-  template <typename T> T* take(size_t n) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += (n * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
-
 // The weight table: 8 global tensors, then 12 per layer, in the order the arenas are carved in (a layer's f16 matrices, its biases, its
 // LayerNorm vectors).  v->layers must have its final size: the table points at its members.
 void build_weights(aph_vit* v) {
   const size_t D = v->D;
-  v->weights.reserve(kGlobalWeights + kLayerWeights * v->L);
-  auto mat = [&](std::string key, size_t rows, size_t cols, half_t** w, half_t** wT, half_t** rep, float** w32, float** wT32) {
-    v->weights.push_back(Weight{std::move(key), rows, cols, {w, wT}, rep, {w32, wT32}, {nullptr, nullptr}});
-  };
-  auto f32 = [&](std::string key, size_t rows, size_t cols, float** w, float** wT = nullptr) {
-    v->weights.push_back(Weight{std::move(key), rows, cols, {nullptr, nullptr}, nullptr, {nullptr, nullptr}, {w, wT}});
-  };
-  mat("conv1.weight", D, v->Kp, &v->w_patch, &v->w_patchT, &v->w_patch2, &v->w_patch32, &v->w_patchT32);
-  f32("class_embedding", 1, D, &v->cls);
-  f32("positional_embedding", v->T, D, &v->pos);
-  f32("ln_pre.weight", 1, D, &v->ln_pre_g); f32("ln_pre.bias", 1, D, &v->ln_pre_b);
-  f32("ln_post.weight", 1, D, &v->ln_post_g); f32("ln_post.bias", 1, D, &v->ln_post_b);
-  f32("proj", D, v->E, &v->proj, &v->projT);
+  std::vector<Weight>& t = v->weights;
+  t.reserve(kGlobalWeights + kLayerWeights * v->L);
+  add_mat(t, "conv1.weight", D, v->Kp, &v->w_patch, &v->w_patchT, &v->w_patch2, &v->w_patch32, &v->w_patchT32);
+  add_f32(t, "class_embedding", 1, D, &v->cls);
+  add_f32(t, "positional_embedding", v->T, D, &v->pos);
+  add_f32(t, "ln_pre.weight", 1, D, &v->ln_pre_g); add_f32(t, "ln_pre.bias", 1, D, &v->ln_pre_b);
+  add_f32(t, "ln_post.weight", 1, D, &v->ln_post_g); add_f32(t, "ln_post.bias", 1, D, &v->ln_post_b);
+  add_f32(t, "proj", D, v->E, &v->proj, &v->projT);
   for (int li = 0; li < v->L; ++li) {
     Layer& l = v->layers[li];
     const std::string p = "transformer.resblocks." + std::to_string(li) + ".";
-    mat(p + "attn.in_proj_weight", 3 * D, D, &l.w_qkv, &l.w_qkvT, &l.w_qkv2, &l.w_qkv32, &l.w_qkvT32);
-    mat(p + "attn.out_proj.weight", D, D, &l.w_o, &l.w_oT, nullptr, &l.w_o32, &l.w_oT32);
-    mat(p + "mlp.c_fc.weight", 4 * D, D, &l.w_fc1, &l.w_fc1T, nullptr, &l.w_fc1_32, &l.w_fc1T32);
-    mat(p + "mlp.c_proj.weight", D, 4 * D, &l.w_fc2, &l.w_fc2T, nullptr, &l.w_fc2_32, &l.w_fc2T32);
-    f32(p + "attn.in_proj_bias", 1, 3 * D, &l.b_qkv); f32(p + "attn.out_proj.bias", 1, D, &l.b_o);
-    f32(p + "mlp.c_fc.bias", 1, 4 * D, &l.b_fc1); f32(p + "mlp.c_proj.bias", 1, D, &l.b_fc2);
-    f32(p + "ln_1.weight", 1, D, &l.ln1_g); f32(p + "ln_1.bias", 1, D, &l.ln1_b);
-    f32(p + "ln_2.weight", 1, D, &l.ln2_g); f32(p + "ln_2.bias", 1, D, &l.ln2_b);
+    add_mat(t, p + "attn.in_proj_weight", 3 * D, D, &l.w_qkv, &l.w_qkvT, &l.w_qkv2, &l.w_qkv32, &l.w_qkvT32);
+    add_mat(t, p + "attn.out_proj.weight", D, D, &l.w_o, &l.w_oT, nullptr, &l.w_o32, &l.w_oT32);
+    add_mat(t, p + "mlp.c_fc.weight", 4 * D, D, &l.w_fc1, &l.w_fc1T, nullptr, &l.w_fc1_32, &l.w_fc1T32);
+    add_mat(t, p + "mlp.c_proj.weight", D, 4 * D, &l.w_fc2, &l.w_fc2T, nullptr, &l.w_fc2_32, &l.w_fc2T32);
+    add_f32(t, p + "attn.in_proj_bias", 1, 3 * D, &l.b_qkv); add_f32(t, p + "attn.out_proj.bias", 1, D, &l.b_o);
+    add_f32(t, p + "mlp.c_fc.bias", 1, 4 * D, &l.b_fc1); add_f32(t, p + "mlp.c_proj.bias", 1, D, &l.b_fc2);
+    add_f32(t, p + "ln_1.weight", 1, D, &l.ln1_g); add_f32(t, p + "ln_1.bias", 1, D, &l.ln1_b);
+    add_f32(t, p + "ln_2.weight", 1, D, &l.ln2_g); add_f32(t, p + "ln_2.bias", 1, D, &l.ln2_b);
   }
 }
 
-enum Arena { ARENA_MAIN, ARENA_HILO, ARENA_F32 };
-// the copies of weights [first, last) that live in arena `a`, in table order
-void carve_weights(aph_vit* v, Carver& c, size_t first, size_t last, Arena a) {
-  for (size_t i = first; i < last; ++i) {
-    Weight& w = v->weights[i];
-    const size_t n = w.rows * w.cols;
-    if (a == ARENA_MAIN) {
-      if (w.h16[0]) { *w.h16[0] = c.take<half_t>(n); *w.h16[1] = c.take<half_t>(n); }
-      else { *w.f32[0] = c.take<float>(n); if (w.f32[1]) *w.f32[1] = c.take<float>(n); }
-    }
-    else if (a == ARENA_HILO) { if (w.rep) *w.rep = c.take<half_t>(2 * n); }
-    else if (w.m32[0]) { *w.m32[0] = c.take<float>(n); *w.m32[1] = c.take<float>(n); }
-  }
-}
+// The carve functions point the handle's members into `base` and return the arena's size; base == nullptr: null pointers, the size alone.
 
 // the second arena (aph_vit_enable_hilo): [N, 2 K] copies of the patch-embedding and QKV weights, every row twice along K -- the B operand of
 // a GEMM over [hi | lo] activation rows.  85 MB at ViT-B/32 that the default (f16 everywhere) path never touches.
-void carve_hilo(aph_vit* v, char* base, size_t* total) {
+size_t carve_hilo(aph_vit* v, char* base) {
   Carver c{base};
-  carve_weights(v, c, 0, v->weights.size(), ARENA_HILO);
-  *total = c.off;
+  carve_weights(v->weights, c, 0, v->weights.size(), ARENA_HILO);
+  return c.off;
 }
 
 // the exact path's arena (aph_vit_enable_f32): fp32 weights [N, K] and transposes, the fp32 stash (per block: qkv, dGELU/du), shared fp32
 // scratch (LayerNorm outputs / their gradients, GELU outputs / du, attention output / its gradient, dqkv, attention row dots) and the split-K
 // partials of the class-row GEMMs.  x_in / x_mid / lse / x0 / x_last / dx of the main arena are fp32 already and are shared with the f16 path.
-void carve_f32(aph_vit* v, char* base, size_t* total) {
+size_t carve_f32(aph_vit* v, char* base) {
   Carver c{base};
   const size_t D = v->D, Mx = (size_t)v->max_batch * v->T;
-  carve_weights(v, c, 0, kGlobalWeights, ARENA_F32);
+  carve_weights(v->weights, c, 0, kGlobalWeights, ARENA_F32);
   for (size_t li = 0; li < v->layers.size(); ++li) {
     Layer& l = v->layers[li];
-    carve_weights(v, c, kGlobalWeights + li * kLayerWeights, kGlobalWeights + (li + 1) * kLayerWeights, ARENA_F32);
+    carve_weights(v->weights, c, kGlobalWeights + li * kLayerWeights, kGlobalWeights + (li + 1) * kLayerWeights, ARENA_F32);
     l.qkv32 = c.take<float>(Mx * 3 * D); l.dg32 = c.take<float>(Mx * 4 * D);
   }
   v->h32 = c.take<float>(Mx * D); v->g32 = c.take<float>(Mx * 4 * D);
@@ -166,17 +126,16 @@ void carve_f32(aph_vit* v, char* base, size_t* total) {
   v->delta32 = c.take<float>((size_t)v->max_batch * v->heads * v->T);
   v->f32sp.ws_floats = (size_t)8 * v->max_batch * 4 * D;
   v->f32sp.ws = c.take<float>(v->f32sp.ws_floats);
-  if (!base) v->f32sp.ws = nullptr;
-  *total = c.off;
+  return c.off;
 }
 
-void carve(aph_vit* v, char* base, size_t* total) {
+size_t carve(aph_vit* v, char* base) {
   Carver c{base};
   const size_t D = v->D, Mx = (size_t)v->max_batch * v->T, T = v->T;
-  carve_weights(v, c, 0, kGlobalWeights, ARENA_MAIN);
+  carve_weights(v->weights, c, 0, kGlobalWeights, ARENA_MAIN);
   for (size_t li = 0; li < v->layers.size(); ++li) {
     Layer& l = v->layers[li];
-    carve_weights(v, c, kGlobalWeights + li * kLayerWeights, kGlobalWeights + (li + 1) * kLayerWeights, ARENA_MAIN);
+    carve_weights(v->weights, c, kGlobalWeights + li * kLayerWeights, kGlobalWeights + (li + 1) * kLayerWeights, ARENA_MAIN);
     l.x_in = c.take<float>(Mx * D); l.x_mid = c.take<float>(Mx * D); l.lse = c.take<float>((size_t)v->max_batch * v->heads * T);
     l.qkv = c.take<half_t>(Mx * 3 * D); l.att = c.take<half_t>(Mx * D); l.u = c.take<half_t>(Mx * 4 * D);
   }
@@ -187,52 +146,13 @@ void carve(aph_vit* v, char* base, size_t* total) {
   v->datt = c.take<half_t>(Mx * D); v->dqkv = c.take<half_t>(Mx * 3 * D); v->dx0_16 = c.take<half_t>(Mx * D);
   v->sk.ws_floats = (size_t)256 * GemmSmall::BM * GemmSmall::BN;       // choose_splits keeps tiles * splits <= 256
   v->sk.ws = c.take<float>(v->sk.ws_floats);
-  *total = c.off;
-}
-
-// host fp32 [rows, cols] -> device fp16, optionally transposed
-int upload_f16(half_t* dst, const float* src, size_t rows, size_t cols, bool transpose) {
-  std::vector<half_t> tmp(rows * cols);
-  if (!transpose) {
-    for (size_t i = 0; i < rows * cols; ++i) tmp[i] = (half_t)src[i];
-  } else {
-    for (size_t r = 0; r < rows; ++r)
-      for (size_t c = 0; c < cols; ++c) tmp[c * rows + r] = (half_t)src[r * cols + c];
-  }
-  return hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(half_t), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-}
-// host fp32 [rows, cols] -> device fp16 [rows, 2 cols]: every row twice along K (the B operand of a hi | lo split GEMM)
-int upload_f16_twice(half_t* dst, const float* src, size_t rows, size_t cols) {
-  std::vector<half_t> tmp(rows * cols * 2);
-  for (size_t r = 0; r < rows; ++r)
-    for (size_t c = 0; c < cols; ++c) tmp[r * 2 * cols + c] = tmp[r * 2 * cols + cols + c] = (half_t)src[r * cols + c];
-  return hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(half_t), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-}
-int upload_f32(float* dst, const float* src, size_t rows, size_t cols, bool transpose) {
-  if (!transpose) return hipMemcpy(dst, src, rows * cols * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-  std::vector<float> tmp(rows * cols);
-  for (size_t r = 0; r < rows; ++r)
-    for (size_t c = 0; c < cols; ++c) tmp[c * rows + r] = src[r * cols + c];
-  return hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+  return c.off;
 }
 
 // host fp32 copy of a weight matrix -> the fp32 arena (when both exist)
 int sync_f32(aph_vit* v, const Weight& w) {
   if (!v->arena_f32 || !w.m32[0] || w.host.empty()) return 0;
   return upload_f32(*w.m32[0], w.host.data(), w.rows, w.cols, false) | upload_f32(*w.m32[1], w.host.data(), w.rows, w.cols, true);
-}
-
-// the checks every forward / backward entry opens with: arguments, batch, every tensor of the table uploaded at least once
-int check_loaded(const aph_vit* v, const char* who) {
-  int n = 0;
-  for (const Weight& w : v->weights) n += w.set;
-  if (n == (int)v->weights.size()) return 0;
-  return aph_fail(APH_ERR_ARG, "%s: weights not fully loaded (%d of %zu tensors)", who, n, v->weights.size());
-}
-int check_call(const aph_vit* v, const void* in, const void* out, int S, const char* who) {
-  if (!v || !in || !out) return aph_fail(APH_ERR_ARG, "%s: null argument", who);
-  if (S < 1 || S > v->max_batch) return aph_fail(APH_ERR_ARG, "%s: batch %d outside 1..%d", who, S, v->max_batch);
-  return check_loaded(v, who);
 }
 
 // a patch side that is no power of two: its patch rows come from aph_patchify_f16_win (padded to aph_patch_row_elems), not from the sampler's
@@ -309,12 +229,7 @@ int aph_vit_create(int input_resolution, int patch_size, int width, int layers, 
   if (v->T > t_max) { delete v; return aph_fail(APH_ERR_UNSUPPORTED, "aph_vit_create: %d tokens per image not supported", v->T); }
   v->layers.resize(layers);
   build_weights(v);
-  size_t total = 0;
-  carve(v, nullptr, &total);
-  const hipError_t me = hipMalloc((void**)&v->arena, total);
-  if (me != hipSuccess) { delete v; return aph_fail(APH_ERR_HIP, "aph_vit_create: cannot allocate %zu bytes (%s)", total, hipGetErrorString(me)); }
-  v->arena_bytes = total;
-  carve(v, v->arena, &total);
+  if (const int rc = alloc_arena("aph_vit_create", &v->arena, &v->arena_bytes, [&](char* base) { return carve(v, base); })) { delete v; return rc; }
   *out = v;
   return APH_OK;
   APH_CATCH
@@ -338,24 +253,13 @@ int aph_vit_enable_hilo(aph_vit* v) {
   if (!v) return aph_fail(APH_ERR_ARG, "aph_vit_enable_hilo: null handle");
   if (v->arena_hilo) return APH_OK;
   if (const int rc = check_f16_only(v, "aph_vit_enable_hilo", "the split-precision forward")) return rc;
-  if (const int rc = check_loaded(v, "aph_vit_enable_hilo")) return rc;
-  size_t total = 0;
-  carve_hilo(v, nullptr, &total);
-  char* base = nullptr;
-  const hipError_t me = hipMalloc((void**)&base, total);
-  if (me != hipSuccess) { carve_hilo(v, nullptr, &total); return aph_fail(APH_ERR_HIP, "aph_vit_enable_hilo: cannot allocate %zu bytes (%s)", total, hipGetErrorString(me)); }
-  carve_hilo(v, base, &total);
-  int rc = 0;
-  for (const Weight& w : v->weights)
-    if (w.rep) rc |= upload_f16_twice(*w.rep, w.host.data(), w.rows, w.cols);
-  if (rc || hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(base);
-    carve_hilo(v, nullptr, &total);          // back to null pointers
-    return aph_fail(APH_ERR_HIP, "aph_vit_enable_hilo: weight upload failed");
-  }
-  v->arena_hilo = base;
-  v->arena_hilo_bytes = total;
-  return APH_OK;
+  if (const int rc = check_loaded(v->weights, "aph_vit_enable_hilo")) return rc;
+  return alloc_arena("aph_vit_enable_hilo", &v->arena_hilo, &v->arena_hilo_bytes, [&](char* base) { return carve_hilo(v, base); }, [&] {
+    int rc = 0;
+    for (const Weight& w : v->weights)
+      if (w.rep) rc |= upload_f16_twice(*w.rep, w.host.data(), w.rows, w.cols);
+    return rc || hipDeviceSynchronize() != hipSuccess;
+  });
   APH_CATCH
 }
 
@@ -367,24 +271,12 @@ int aph_vit_enable_f32(aph_vit* v) {
   if (!v) return aph_fail(APH_ERR_ARG, "aph_vit_enable_f32: null handle");
   if (v->arena_f32) return APH_OK;
   if (const int rc = check_f16_only(v, "aph_vit_enable_f32", "the exact fp32 path")) return rc;
-  if (const int rc = check_loaded(v, "aph_vit_enable_f32")) return rc;
-  size_t total = 0;
-  carve_f32(v, nullptr, &total);
-  char* base = nullptr;
-  const hipError_t me = hipMalloc((void**)&base, total);
-  if (me != hipSuccess) return aph_fail(APH_ERR_HIP, "aph_vit_enable_f32: cannot allocate %zu bytes (%s)", total, hipGetErrorString(me));
-  carve_f32(v, base, &total);
-  v->arena_f32 = base;
-  int rc = 0;
-  for (const Weight& w : v->weights) rc |= sync_f32(v, w);
-  if (rc || hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(base);
-    v->arena_f32 = nullptr;
-    carve_f32(v, nullptr, &total);           // back to null pointers
-    return aph_fail(APH_ERR_HIP, "aph_vit_enable_f32: weight upload failed");
-  }
-  v->arena_f32_bytes = total;
-  return APH_OK;
+  if (const int rc = check_loaded(v->weights, "aph_vit_enable_f32")) return rc;
+  return alloc_arena("aph_vit_enable_f32", &v->arena_f32, &v->arena_f32_bytes, [&](char* base) { return carve_f32(v, base); }, [&] {
+    int rc = 0;
+    for (const Weight& w : v->weights) rc |= sync_f32(v, w);      // (reads v->arena_f32: alloc_arena has set it)
+    return rc || hipDeviceSynchronize() != hipSuccess;
+  });
   APH_CATCH
 }
 
@@ -395,9 +287,7 @@ size_t aph_vit_workspace_bytes(const aph_vit* v) { return v ? v->arena_bytes + v
 int aph_vit_set_weight(aph_vit* v, const char* name, const float* data, size_t count) {
   APH_TRY
   if (!v || !name || !data) return aph_fail(APH_ERR_ARG, "aph_vit_set_weight: null argument");
-  Weight* w = nullptr;
-  for (Weight& e : v->weights)
-    if (e.key == name) { w = &e; break; }
+  Weight* w = find_weight(v->weights, name);
   if (!w) return aph_fail(APH_ERR_ARG, "aph_vit_set_weight: unknown key %s", name);
   const size_t rows = w->rows, cols = w->cols;
   const bool conv1 = w->key == "conv1.weight";
@@ -448,12 +338,12 @@ static int vit_forward_impl(aph_vit* v, const void* d_patches, int S, float* d_e
   v->sk.small_batch = M <= 128;   // see gemm_rs_mode(): the split-K small-M kernel only when the whole batch is small
   vgemm(v, (const half_t*)d_patches, kx * v->Kp, hilo ? v->w_patch2 : v->w_patch, kx * v->Kp, S * v->P, D, kx * v->Kp, EpiPatchEmbed{v->x0, v->pos, D, v->P, T}, st, kx);
   const bool fuse = vit_fuse_ln() != 0;
-  launch_ln_fwd<false, true>(nv, v->x0, v->ln_pre_g, v->ln_pre_b, v->layers[0].x_in, M, T, v->cls, v->pos, v->x0, st, 1,
-                             fuse ? v->layers[0].ln1_g : nullptr, fuse ? v->layers[0].ln1_b : nullptr, fuse ? v->h : nullptr, hilo ? 1 : 0);
+  launch_ln_fwd<false, true>(nv, {.x = v->x0, .g = v->ln_pre_g, .b = v->ln_pre_b, .out = v->layers[0].x_in, .M = M, .T = T, .cls = v->cls, .pos = v->pos, .x_fill = v->x0,
+                                  .g2 = fuse ? v->layers[0].ln1_g : nullptr, .b2 = fuse ? v->layers[0].ln1_b : nullptr, .out2 = fuse ? v->h : nullptr, .hilo = hilo ? 1 : 0}, st);
   for (int li = 0; li < v->L; ++li) {
     Layer& l = v->layers[li];
     float* x_next = li + 1 < v->L ? v->layers[li + 1].x_in : v->x_last;
-    if (!(fuse && li == 0)) launch_ln_fwd<true, false>(nv, l.x_in, l.ln1_g, l.ln1_b, v->h, M, T, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, hilo ? 1 : 0);
+    if (!(fuse && li == 0)) launch_ln_fwd<true, false>(nv, {.x = l.x_in, .g = l.ln1_g, .b = l.ln1_b, .out = v->h, .M = M, .T = T, .hilo = hilo ? 1 : 0}, st);
     if (hilo) {
       // [r5] the lo half reaches the Q and K columns only; the V columns are summed over the hi half of the [hi | lo] rows alone (the first D of
       // the 2 D columns of A and of [W | W]).  What the lo half repairs is the cancellation in h . W on weights whose residual stream carries
@@ -478,7 +368,7 @@ static int vit_forward_impl(aph_vit* v, const void* d_patches, int S, float* d_e
     const bool cls_only = li + 1 == v->L;
     const int Mr = cls_only ? S : M, rs = cls_only ? T : 1;
     vgemm(v, l.att, rs * D, l.w_o, D, Mr, D, D, EpiResidual{l.x_mid, l.x_in, rs * D, l.b_o}, st);
-    launch_ln_fwd<true, false>(nv, l.x_mid, l.ln2_g, l.ln2_b, v->h, Mr, T, nullptr, nullptr, nullptr, st, rs);
+    launch_ln_fwd<true, false>(nv, {.x = l.x_mid, .g = l.ln2_g, .b = l.ln2_b, .out = v->h, .M = Mr, .T = T, .xs = rs}, st);
     vgemm(v, v->h, D, l.w_fc1, D, Mr, 4 * D, D, EpiGelu{l.u, v->gact, 4 * D, l.b_fc1}, st);
     vgemm(v, v->gact, 4 * D, l.w_fc2, 4 * D, Mr, D, 4 * D, EpiResidual{x_next, l.x_mid, rs * D, l.b_fc2}, st);
   }
@@ -521,19 +411,20 @@ static int vit_backward_impl(aph_vit* v, const float* d_genc, int S, void* d_pat
     if (cls_only) zero_fill_async(v->datt, sizeof(half_t) * (size_t)M * D, st);   // no gradient into the other rows' attention output
     vgemm(v, v->dx16, rs * D, l.w_fc2T, D, Mr, 4 * D, D, EpiGeluBwd{v->du, l.u, 4 * D}, st);
     vgemm(v, v->du, 4 * D, l.w_fc1T, 4 * D, Mr, D, 4 * D, EpiF16{v->dh, D, nullptr}, st);
-    if (s16) launch_ln_bwd<true, false>(nv, v->dh, l.x_mid, l.ln2_g, v->dx16, nullptr, v->dx16, Mr, T, st, rs, 0, nullptr, nullptr, 1);
-    else launch_ln_bwd<true, false>(nv, v->dh, l.x_mid, l.ln2_g, v->dx, v->dx, v->dx16, Mr, T, st, rs);
+    if (s16) launch_ln_bwd<true, false>(nv, {.dy = v->dh, .x = l.x_mid, .g = l.ln2_g, .res = v->dx16, .out16 = v->dx16, .M = Mr, .T = T, .xs = rs, .res_f16 = 1}, st);
+    else launch_ln_bwd<true, false>(nv, {.dy = v->dh, .x = l.x_mid, .g = l.ln2_g, .res = v->dx, .out32 = v->dx, .out16 = v->dx16, .M = Mr, .T = T, .xs = rs}, st);
     vgemm(v, v->dx16, rs * D, l.w_oT, D, Mr, D, D, EpiF16{v->datt, rs * D, nullptr}, st);
     launch_attn_bwd(attn_args(v, l, S), st);
     vgemm(v, v->dqkv, 3 * D, l.w_qkvT, 3 * D, M, D, 3 * D, EpiF16{v->dh, D, nullptr}, st);
     if (fuse && li == 0)      // ln_1 backward and ln_pre backward as one kernel: writes the patch rows of dx0_16 only
-      launch_ln_bwd<true, false>(nv, v->dh, l.x_in, l.ln1_g, s16 ? (const void*)v->dx16 : (const void*)v->dx, nullptr, v->dx0_16, M, T, st, 1, cls_only ? T : 0, v->x0, v->ln_pre_g, s16);
+      launch_ln_bwd<true, false>(nv, {.dy = v->dh, .x = l.x_in, .g = l.ln1_g, .res = s16 ? (const void*)v->dx16 : (const void*)v->dx, .out16 = v->dx0_16, .M = M, .T = T,
+                                      .res_T = cls_only ? T : 0, .x_b = v->x0, .g_b = v->ln_pre_g, .res_f16 = s16}, st);
     else if (s16)
-      launch_ln_bwd<true, false>(nv, v->dh, l.x_in, l.ln1_g, v->dx16, nullptr, v->dx16, M, T, st, 1, cls_only ? T : 0, nullptr, nullptr, 1);
+      launch_ln_bwd<true, false>(nv, {.dy = v->dh, .x = l.x_in, .g = l.ln1_g, .res = v->dx16, .out16 = v->dx16, .M = M, .T = T, .res_T = cls_only ? T : 0, .res_f16 = 1}, st);
     else
-      launch_ln_bwd<true, false>(nv, v->dh, l.x_in, l.ln1_g, v->dx, v->dx, v->dx16, M, T, st, 1, (fuse && cls_only) ? T : 0);
+      launch_ln_bwd<true, false>(nv, {.dy = v->dh, .x = l.x_in, .g = l.ln1_g, .res = v->dx, .out32 = v->dx, .out16 = v->dx16, .M = M, .T = T, .res_T = (fuse && cls_only) ? T : 0}, st);
   }
-  if (!fuse) launch_ln_bwd<false, true>(nv, v->dx, v->x0, v->ln_pre_g, nullptr, nullptr, v->dx0_16, M, T, st);
+  if (!fuse) launch_ln_bwd<false, true>(nv, {.dy = v->dx, .x = v->x0, .g = v->ln_pre_g, .out16 = v->dx0_16, .M = M, .T = T}, st);
   if (grad_f16) vgemm(v, v->dx0_16, D, v->w_patchT, D, S * v->P, v->Kp, D, EpiF16Scale{(half_t*)d_patch_grad, v->Kp, out_scale}, st);
   else vgemm(v, v->dx0_16, D, v->w_patchT, D, S * v->P, v->Kp, D, EpiF32{(float*)d_patch_grad, v->Kp, out_scale}, st);
   return aph_check_launch("aph_vit_backward");
@@ -563,17 +454,17 @@ int aph_vit_forward_f32(aph_vit* v, const float* d_patches, int S, float* d_enc,
   hipStream_t st = (hipStream_t)stream_;
   const int D = v->D, T = v->T, M = S * T, nv = D / 256;
   vgemm32(v, d_patches, v->Kp, v->w_patch32, v->Kp, S * v->P, D, v->Kp, EpiPatchEmbed{v->x0, v->pos, D, v->P, T}, st);
-  launch_ln_fwd<false, true>(nv, v->x0, v->ln_pre_g, v->ln_pre_b, v->layers[0].x_in, M, T, v->cls, v->pos, v->x0, st);
+  launch_ln_fwd<false, true>(nv, {.x = v->x0, .g = v->ln_pre_g, .b = v->ln_pre_b, .out = v->layers[0].x_in, .M = M, .T = T, .cls = v->cls, .pos = v->pos, .x_fill = v->x0}, st);
   for (int li = 0; li < v->L; ++li) {
     Layer& l = v->layers[li];
     float* x_next = li + 1 < v->L ? v->layers[li + 1].x_in : v->x_last;
-    launch_ln_fwd<false, false>(nv, l.x_in, l.ln1_g, l.ln1_b, v->h32, M, T, nullptr, nullptr, nullptr, st);
+    launch_ln_fwd<false, false>(nv, {.x = l.x_in, .g = l.ln1_g, .b = l.ln1_b, .out = v->h32, .M = M, .T = T}, st);
     vgemm32(v, v->h32, D, l.w_qkv32, D, M, 3 * D, D, EpiBiasF32{l.qkv32, 3 * D, l.b_qkv}, st);
     launch_attn_fwd_f32(l.qkv32, v->att32, l.lse, S, T, v->heads, st);
     const bool cls_only = li + 1 == v->L;
     const int Mr = cls_only ? S : M, rs = cls_only ? T : 1;
     vgemm32(v, v->att32, rs * D, l.w_o32, D, Mr, D, D, EpiResidual{l.x_mid, l.x_in, rs * D, l.b_o}, st);
-    launch_ln_fwd<false, false>(nv, l.x_mid, l.ln2_g, l.ln2_b, v->h32, Mr, T, nullptr, nullptr, nullptr, st, rs);
+    launch_ln_fwd<false, false>(nv, {.x = l.x_mid, .g = l.ln2_g, .b = l.ln2_b, .out = v->h32, .M = Mr, .T = T, .xs = rs}, st);
     vgemm32(v, v->h32, D, l.w_fc1_32, D, Mr, 4 * D, D, EpiGeluF32{l.dg32, v->g32, 4 * D, l.b_fc1}, st);
     vgemm32(v, v->g32, 4 * D, l.w_fc2_32, 4 * D, Mr, D, 4 * D, EpiResidual{x_next, l.x_mid, rs * D, l.b_fc2}, st);
   }
@@ -605,15 +496,15 @@ int aph_vit_backward_f32(aph_vit* v, const float* d_genc, int S, float* d_patch_
     if (cls_only) zero_fill_async(v->datt32, sizeof(float) * (size_t)M * D, st);      // no gradient into the other rows' attention output
     vgemm32(v, v->dx, rs * D, l.w_fc2T32, D, Mr, 4 * D, D, EpiGeluBwdF32{du, l.dg32, 4 * D}, st);
     vgemm32(v, du, 4 * D, l.w_fc1T32, 4 * D, Mr, D, 4 * D, EpiF32{dh, D, 1.0f}, st);
-    launch_ln_bwd<false, false>(nv, dh, l.x_mid, l.ln2_g, v->dx, v->dx, nullptr, Mr, T, st, rs);
+    launch_ln_bwd<false, false>(nv, {.dy = dh, .x = l.x_mid, .g = l.ln2_g, .res = v->dx, .out32 = v->dx, .M = Mr, .T = T, .xs = rs}, st);
     vgemm32(v, v->dx, rs * D, l.w_oT32, D, Mr, D, D, EpiF32{v->datt32, rs * D, 1.0f}, st);
     launch_attn_bwd_f32(l.qkv32, v->datt32, l.lse, v->delta32, v->dqkv32, S, T, v->heads, st);
     vgemm32(v, v->dqkv32, 3 * D, l.w_qkvT32, 3 * D, M, D, 3 * D, EpiF32{dh, D, 1.0f}, st);
     // the last block's residual reaches its class rows only (res_T = T): the other rows of dx are not read before this writes them
-    launch_ln_bwd<false, false>(nv, dh, l.x_in, l.ln1_g, v->dx, v->dx, nullptr, M, T, st, 1, cls_only ? T : 0);
+    launch_ln_bwd<false, false>(nv, {.dy = dh, .x = l.x_in, .g = l.ln1_g, .res = v->dx, .out32 = v->dx, .M = M, .T = T, .res_T = cls_only ? T : 0}, st);
   }
   // ln_pre backward into dh (token rows), then the patch-embedding dgrad over its patch rows (row s*P + p <- token row s*T + 1 + p)
-  launch_ln_bwd<false, false>(nv, v->dx, v->x0, v->ln_pre_g, nullptr, dh, nullptr, M, T, st);
+  launch_ln_bwd<false, false>(nv, {.dy = v->dx, .x = v->x0, .g = v->ln_pre_g, .out32 = dh, .M = M, .T = T}, st);
   vgemm32(v, dh, D, v->w_patchT32, D, S * v->P, v->Kp, D, EpiF32{d_patch_grad, v->Kp, out_scale}, st, v->P);
   return aph_check_launch("aph_vit_backward_f32");
   APH_CATCH

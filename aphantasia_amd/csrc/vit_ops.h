@@ -345,20 +345,34 @@ inline void ln_with_nv(int nv, F&& f) {
     default: f(std::integral_constant<int, 4>{}); break;
   }
 }
-// g2 / b2 / out2: the next LayerNorm of the same rows fused behind this one (ln_fwd_kernel)
+// The arguments of a LayerNorm launch, filled by field name at the call site (in the order declared here); what a call leaves out is the plain
+// launch: every row (xs = 1), no class-row fill, no fused second LayerNorm, f16 rows of D (hilo = 0).
+// cls / pos / x_fill: with CLS only;  g2 / b2 / out2: the next LayerNorm of the same rows fused behind this one (ln_fwd_kernel)
+struct LnFwd {
+  const float *x, *g, *b; void* out; int M, T;
+  const float *cls = nullptr, *pos = nullptr; float* x_fill = nullptr;
+  int xs = 1;
+  const float *g2 = nullptr, *b2 = nullptr; half_t* out2 = nullptr;
+  int hilo = 0;
+};
 template <bool OUT_F16, bool CLS>
-void launch_ln_fwd(int nv, const float* x, const float* g, const float* b, void* out, int M, int T, const float* cls,
-                   const float* pos, float* x_fill, hipStream_t st, int xs = 1, const float* g2 = nullptr, const float* b2 = nullptr,
-                   half_t* out2 = nullptr, int hilo = 0) {
-  const dim3 grid((M + 3) / 4), block(256);
-  ln_with_nv(nv, [&](auto NV) { APH_LAUNCH((ln_fwd_kernel<decltype(NV)::value, OUT_F16, CLS>), grid, block, 0, st, x, g, b, out, M, T, cls, pos, x_fill, xs, g2, b2, out2, hilo); });
+void launch_ln_fwd(int nv, const LnFwd& a, hipStream_t st) {
+  const dim3 grid((a.M + 3) / 4), block(256);
+  ln_with_nv(nv, [&](auto NV) { APH_LAUNCH((ln_fwd_kernel<decltype(NV)::value, OUT_F16, CLS>), grid, block, 0, st, a.x, a.g, a.b, a.out, a.M, a.T, a.cls, a.pos, a.x_fill, a.xs, a.g2, a.b2, a.out2, a.hilo); });
 }
-// res_T: residual on the rows with row % res_T == 0 only;  x_b / g_b: the previous LayerNorm's backward fused behind this one (ln_bwd_kernel)
+// res_T: residual on the rows with row % res_T == 0 only;  x_b / g_b: the previous LayerNorm's backward fused behind this one (ln_bwd_kernel);
+// left out: no residual, no output of that kind, every row (xs = 1, res_T = 0), no fused pair, an fp32 residual (res_f16 = 0)
+struct LnBwd {
+  const void* dy; const float *x, *g;
+  const void* res = nullptr; float* out32 = nullptr; half_t* out16 = nullptr;
+  int M, T, xs = 1, res_T = 0;
+  const float *x_b = nullptr, *g_b = nullptr;
+  int res_f16 = 0;
+};
 template <bool DY_F16, bool PATCH>
-void launch_ln_bwd(int nv, const void* dy, const float* x, const float* g, const void* res, float* out32, half_t* out16, int M,
-                   int T, hipStream_t st, int xs = 1, int res_T = 0, const float* x_b = nullptr, const float* g_b = nullptr, int res_f16 = 0) {
-  const dim3 grid((M + 3) / 4), block(256);
-  ln_with_nv(nv, [&](auto NV) { APH_LAUNCH((ln_bwd_kernel<decltype(NV)::value, DY_F16, PATCH>), grid, block, 0, st, dy, x, g, res, out32, out16, M, T, xs, res_T, x_b, g_b, res_f16); });
+void launch_ln_bwd(int nv, const LnBwd& a, hipStream_t st) {
+  const dim3 grid((a.M + 3) / 4), block(256);
+  ln_with_nv(nv, [&](auto NV) { APH_LAUNCH((ln_bwd_kernel<decltype(NV)::value, DY_F16, PATCH>), grid, block, 0, st, a.dy, a.x, a.g, a.res, a.out32, a.out16, a.M, a.T, a.xs, a.res_T, a.x_b, a.g_b, a.res_f16); });
 }
 // x [S * T, D] (class rows read) -> enc [S, E]
 inline void launch_head_fwd(const float* x, const float* g, const float* b, const float* proj, float* enc, int S, int T, int D, int E, hipStream_t st) {

@@ -284,13 +284,15 @@ int aph_ln_test(int mode, int D, int M, int T, int xs, int res_T, int flags, con
   if (!ok) return aph_fail(APH_ERR_ARG, "aph_ln_test: bad argument (mode %d, D=%d M=%d T=%d xs=%d flags=%d)", mode, D, M, T, xs, flags);
   hipStream_t st = (hipStream_t)stream_;
   if (mode == 0)
-    launch_ln_fwd<false, true>(nv, d_x, d_g, d_b, d_out, M, T, d_cls, d_pos, d_x_fill, st, 1, d_g2, d_b2, (half_t*)d_out2, hilo);
+    launch_ln_fwd<false, true>(nv, {.x = d_x, .g = d_g, .b = d_b, .out = d_out, .M = M, .T = T, .cls = d_cls, .pos = d_pos, .x_fill = d_x_fill,
+                                    .g2 = d_g2, .b2 = d_b2, .out2 = (half_t*)d_out2, .hilo = hilo}, st);
   else if (mode == 1)
-    launch_ln_fwd<true, false>(nv, d_x, d_g, d_b, d_out, M, T, nullptr, nullptr, nullptr, st, xs, nullptr, nullptr, nullptr, hilo);
+    launch_ln_fwd<true, false>(nv, {.x = d_x, .g = d_g, .b = d_b, .out = d_out, .M = M, .T = T, .xs = xs, .hilo = hilo}, st);
   else if (mode == 2)
-    launch_ln_bwd<true, false>(nv, d_dy, d_x, d_g, d_res, (float*)d_out, (half_t*)d_out2, M, T, st, xs, res_T, d_x2, d_g2, res_f16);
+    launch_ln_bwd<true, false>(nv, {.dy = d_dy, .x = d_x, .g = d_g, .res = d_res, .out32 = (float*)d_out, .out16 = (half_t*)d_out2, .M = M, .T = T,
+                                    .xs = xs, .res_T = res_T, .x_b = d_x2, .g_b = d_g2, .res_f16 = res_f16}, st);
   else
-    launch_ln_bwd<false, true>(nv, d_dy, d_x, d_g, nullptr, nullptr, (half_t*)d_out2, M, T, st);
+    launch_ln_bwd<false, true>(nv, {.dy = d_dy, .x = d_x, .g = d_g, .out16 = (half_t*)d_out2, .M = M, .T = T}, st);
   return aph_check_launch("aph_ln_test");
   APH_CATCH
 }
