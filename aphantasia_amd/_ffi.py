@@ -71,6 +71,18 @@ _PROTOTYPES = {
     'aph_text_workspace_bytes': (c_size_t, [c_void_p]),
     'aph_text_set_weight': (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
     'aph_text_forward': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'aph_lpips_create': (c_int, [POINTER(c_int), c_int, c_int, POINTER(c_void_p)]),
+    'aph_lpips_destroy': (c_int, [c_void_p]),
+    'aph_lpips_workspace_bytes': (c_size_t, [c_void_p]),
+    'aph_lpips_set_weight': (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
+    'aph_lpips_set_target': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'aph_lpips_value_grad': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aph_lpips_value_grad_half': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aph_lpips_pack_test': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t]),
+    'aph_lpips_conv_test': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'aph_lpips_pool_test': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aph_lpips_head_test': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aph_lpips_resize_test': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'aph_frame_affine': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_void_p]),
     'aph_patchify_f16': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_patchify_f16_hilo': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -104,13 +104,15 @@ class SkipGuard:
         return new, mine
 
 
-def step_input_parts(Sl, geometric, second):
+def step_input_parts(Sl, geometric, second, sync=False):
     """(name, shape, dtype) of the per-step host inputs of a shard of Sl cuts: Adam scalars | crop table | augment table
-    [| a second, independently drawn set for --enforce]"""
+    [| a second, independently drawn set for --enforce] [| the step's weight of the --sync term, last: every other layout is unchanged]"""
     cuts = [('table', (Sl, 3), torch.int32)] + ([('aug', (Sl, _ffi.APH_AUG_STRIDE), torch.float32)] if geometric else [])
     parts = [('hyper', (8,), torch.float32)] + cuts
     if second:
         parts += [(name + '2', shape, dt) for name, shape, dt in cuts]
+    if sync:
+        parts.append(('sync', (1,), torch.float32))
     return parts
 
 
@@ -162,7 +164,7 @@ class Engine:
                  lr=0.05, optimizer='adam_custom', align='uniform', macro=0.4, transform=None,
                  size=None, rank=0, world=1, process_group=None, comm=None, param_kind='fft', decorrelate=True, lib=None, state=None, dwt=None, rng='bulk', use_graph=True,
                  rgb_priors=None, fixcontrast=False, sharp=0.0, expand=0.0, enforce=0.0, grad_f16=False, loss_scale=None, reduce_always=False, aest=None,
-                 precise=False, graph_allreduce=None, exact=False, cppn=None):
+                 precise=False, graph_allreduce=None, exact=False, cppn=None, sync=None):
         """params: the leaf tensor ([1,3,h,w//2+1,2] spectrum for 'fft', [1,3,h,w] for 'pixel', the flat
         coefficient buffer for 'dwt' with dwt = its aphantasia_amd.dwt.DWTSynth, the flat weight buffer for 'cppn' with cppn = its
         aphantasia_amd.cppn.CPPNSynth -- the network's sigmoid output is the image: `colors`, `decay`, `decorrelate`, contrast and shift
@@ -180,7 +182,11 @@ class Engine:
         graph_allreduce: with world > 1 and a direct RCCL `comm`, capture the whole step INCLUDING its all-reduce into one hipGraph.  OPT-IN
         (default: the environment's APH_MULTIRANK_GRAPH=1, else off -> multi-rank steps launch eagerly): until that path has executed on a
         real multi-GPU node a hang inside the capture or its collectives would take a run down without an exception to catch (ADVICE r5);
-        bench.py tries it as the first rung of a parent-supervised ladder, which CAN end a hang."""
+        bench.py tries it as the first rung of a parent-supervised ladder, which CAN end a hang.
+        sync: the --sync term (clip_fft.py:268-270): an aphantasia_amd.lpips.LPIPS of this frame size with its target set; each step adds
+        sync_weight x LPIPS(resize(image), target) to the loss and its gradient to the image gradient.  The weight travels in the per-step
+        upload and the kernels read it from the device, so a captured step replays with the weight of ITS step.  A replicated term: with
+        world > 1 only rank 0 adds it.  None: the step issues exactly the launches it issues without the feature."""
         # ---- arguments and refusals
         self.params = params
         self.dev = params.device
@@ -231,6 +237,7 @@ class Engine:
         self.fixcontrast = bool(fixcontrast)
         self.sharp, self.expand = float(sharp), float(expand)       # clip_fft.py:269-270, :276-280
         self.enforce = float(enforce)                               # clip_fft.py:271-275
+        self.sync = sync
         # static loss scale of the fp16 backward with back-off: an overflowed step is skipped on the device and counted (SkipGuard);
         # the host looks at the count every GUARD_EVERY steps and halves the scale
         self.loss_scale = float(LOSS_SCALE if loss_scale is None else loss_scale)
@@ -259,6 +266,8 @@ class Engine:
                 raise NotImplementedError("Engine: rgb_priors are not part of the CPPN path (cppn.py has no such term)")
             h, w = cppn.H, cppn.W                # (its workspace -- stash and gradient partials -- was allocated with it)
         self.h, self.w = h, w
+        if sync is not None and ((sync.H, sync.W) != (h, w) or not sync.has_target):
+            raise ValueError('Engine: sync must be an LPIPS term of the %d x %d frame (it is %d x %d) with its target set' % (h, w, sync.H, sync.W))
         # ---- optimiser state; `state=other.state()` shares it (the --dualmod engines, clip_fft.py:243-252)
         self.lr = lr
         self.beta1, self.wd, self.decoupled, self.amsgrad = optimizer_flags(optimizer)
@@ -310,8 +319,9 @@ class Engine:
             self.ws2 = torch.empty(Sl * 3, **f32)
             self.enf_coef = torch.tensor([-self.enforce], **f32)
         # ---- step inputs (absent ones are None) and the skipped-step guard
-        self.inputs = StepInputs(step_input_parts(Sl, self.geometric, self.enforce != 0), self.dev)
+        self.inputs = StepInputs(step_input_parts(Sl, self.geometric, self.enforce != 0, self.sync is not None), self.dev)
         self.hyper, self.table, self.aug, self.table2, self.aug2 = (self.inputs.views.get(k) for k in ('hyper', 'table', 'aug', 'table2', 'aug2'))
+        self.sync_w = self.inputs.views.get('sync')
         self._guard = SkipGuard(self.dev)
         self.guard = self._guard.count             # the device tensor itself (handed to the guarded Adam)
 
@@ -466,6 +476,8 @@ class Engine:
                    ops.ptr(self.prior_ws), ops.ptr(self.loss), ops.ptr(self.grgb), st)
         if self.sharp != 0 and self.kind != 'dwt' and self.rank == 0:      # `a.sharp != 0 and a.dwt is not True` (clip_fft.py:269)
             L.call('aph_rgb_sharp', ops.ptr(self.rgb), self.h, self.w, -self.sharp, ops.ptr(self.prior_ws), ops.ptr(self.loss), ops.ptr(self.grgb), st)
+        if self.sync is not None and self.rank == 0:                       # clip_fft.py:268-270; replicated term -> one rank adds it
+            self.sync.value_grad(self.rgb, self.sync_w, self.loss, self.grgb, st)
         self._synth_backward(L, st)
 
     def _synth_backward(self, L, st):
@@ -628,8 +640,11 @@ class Engine:
         self._graph = g
 
     # ------------------------------------------------------------------ the step
-    def step(self, table=None, augs=None, lr=None, shift=None, tables2=None):
-        """One train(i).  Returns the (device) loss tensor of THIS step -- do not .item() it every step."""
+    def step(self, table=None, augs=None, lr=None, shift=None, tables2=None, sync_weight=None):
+        """One train(i).  Returns the (device) loss tensor of THIS step -- do not .item() it every step.
+        sync_weight: this step's weight of the --sync term (engines built with sync=...; default 1)."""
+        if sync_weight is not None and self.sync is None:
+            raise ValueError('Engine.step: sync_weight given, but the engine was built without a sync term')
         if self.world > 1 and self.params.is_cuda:
             # Multi-rank: the step (and with it the RCCL all-reduce) runs on a stream of its own rather than on the legacy
             # default (NULL) stream, whose implicit synchronisation with every blocking stream is a bad neighbour for a
@@ -639,12 +654,12 @@ class Engine:
             cur = torch.cuda.current_stream(self.dev)
             self._own_stream.wait_stream(cur)
             with torch.cuda.stream(self._own_stream):
-                out = self._step(table, augs, lr, shift, tables2)
+                out = self._step(table, augs, lr, shift, tables2, sync_weight)
             cur.wait_stream(self._own_stream)
             return out
-        return self._step(table, augs, lr, shift, tables2)
+        return self._step(table, augs, lr, shift, tables2, sync_weight)
 
-    def _step_items(self, hy, table, augs, table2, augs2):
+    def _step_items(self, hy, table, augs, table2, augs2, sync_weight=None):
         """this rank's rows of the step's host inputs, as StepInputs.upload takes them"""
         rows = lambda a: torch.from_numpy(np.ascontiguousarray(a[self.lo:self.hi]))
         packed = lambda a: rows(a) if isinstance(a, np.ndarray) else pack_aug(a[self.lo:self.hi])
@@ -657,9 +672,11 @@ class Engine:
                 items.append(('table2', rows(table2)))
                 if self.geometric:
                     items.append(('aug2', packed(augs2)))
+        if self.sync is not None:
+            items.append(('sync', torch.tensor([1.0 if sync_weight is None else float(sync_weight)], dtype=torch.float32)))
         return items
 
-    def _step(self, table, augs, lr, shift, tables2):
+    def _step(self, table, augs, lr, shift, tables2, sync_weight=None):
         if table is None:
             table, augs = self.draw()
         table2 = augs2 = None
@@ -669,7 +686,7 @@ class Engine:
         self._calls += 1
         lr = self.lr if lr is None else lr
         hy = ops.adam_hyper(self._state['step'][0], lr, self.beta1, 0.999, 1e-8, self.wd, 1.0)
-        self.inputs.upload(self._step_items(hy, table, augs, table2, augs2))
+        self.inputs.upload(self._step_items(hy, table, augs, table2, augs2, sync_weight))
         self._check_overflow()
         use_graph = self.use_graph and shift is None and self.params.is_cuda
         if self._graph is not None and self._vit_handle is not self.visual.handle:

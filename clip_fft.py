@@ -9,7 +9,9 @@ unseeded), --no_save (skip the per-step JPEG, for timing).
 
 The whole loss -- text / style / subtract prompts, a reference image, any --sim, --sharp, --enforce, --expand, --noise and
 --aest (with --aest-weights: the LAION linear head cannot be downloaded here) -- runs through the fused HIP engine
-(aphantasia_amd/engine.py).  --sync (LPIPS: a separate VGG network) is not part of this path.
+(aphantasia_amd/engine.py), and so does --sync: the LPIPS (VGG-16) term against the -i image runs on HIP kernels of its own
+(aphantasia_amd/lpips.py) inside the step; --vgg-weights / --lpips-weights name its two LOCAL weight files (torchvision's vgg16 state dict
+and the lpips package's vgg.pth), without them seeded synthetic weights are used with a warning.
 """
 import argparse
 import os
@@ -22,6 +24,7 @@ import warnings
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -85,6 +88,9 @@ def get_args(argv=None):
     parser.add_argument(       '--aest-weights', dest='aest_weights', default=None, help="state dict of the LAION aesthetic head (sa_0_4_vit_b_32_linear.pth: "
                                "{'weight': [1,512], 'bias': [1]}); upstream downloads it (utils.py:402-413), there is no network here")
     parser.add_argument(       '--aest-weights2', dest='aest_weights2', default=None, help='the head of the --dualmod model (sa_0_4_vit_b_16_linear.pth)')
+    parser.add_argument(       '--vgg-weights', dest='vgg_weights', default=None, help='--sync: torchvision vgg16 state dict (features.N.weight / .bias), a local file; '
+                               'upstream lets the lpips package download it, there is no network here')
+    parser.add_argument(       '--lpips-weights', dest='lpips_weights', default=None, help="--sync: the lpips package's weights/v0.1/vgg.pth (linL.model.1.weight), a local file")
     parser.add_argument(       '--rng',     default=None, choices=['bulk', 'reference'], help="host random draws: 'reference' = the reference's exact draw "
                                "order on torch's / numpy's global generators (a seeded run reproduces the reference's crop and augment tables); "
                                "'bulk' = vectorised draws from a numpy Generator (same distributions, a different stream, ~10x less host time). "
@@ -226,6 +232,11 @@ def _spawn_rank(local_rank, argv, world, port, run_id):
     main(argv)
 
 
+def prog_sync(i, n):
+    """the --sync term's decay over the run (clip_fft.py:269): (N - i) / N with N = steps // opt_step"""
+    return (n - i) / n
+
+
 def main(argv=None):
     a = get_args(argv)
     # ---- multi-GPU (SURVEY.md section 8e; the reference is single-GPU): the cuts are split over the ranks of one node, one process
@@ -300,6 +311,7 @@ def main(argv=None):
     trform_f = pick_transform(a.transform)
     out_name = []
     targets, targets2 = [], []          # (embedding, coef) for model 1 / model 2
+    img_in = None
     if a.in_txt is not None:
         if a.verbose is True: print(' topic text: ', a.in_txt)
         targets += [(e, sign * w) for e, w in enc_text(a.in_txt)]
@@ -334,9 +346,6 @@ def main(argv=None):
     tempdir = os.path.join(a.out_dir, out_name)
     os.makedirs(tempdir, exist_ok=True)
 
-    if a.sync != 0:
-        raise SystemExit(' --sync (LPIPS: a separate VGG network, clip_fft.py:268-270) is not part of the MI355X path')
-
     def load_aest(path):                                                              # utils.py:402-413 aesthetic_model()
         if a.aest == 0:
             return None
@@ -358,9 +367,22 @@ def main(argv=None):
     if a.dwt is True:
         pk = dict(param_kind='dwt', dwt=image_f.synth)
         leaf = image_f.flat
+        h, w = image_f.synth.H, image_f.synth.W
     else:
         pk = dict(param_kind='fft')
         leaf = params[0]
+    # --sync (clip_fft.py:219-222, 268-270): LPIPS between the half-size image and the half-size -i image, inside the fused step
+    sync = None
+    if a.sync > 0:
+        if img_in is None:
+            print(' --sync: no readable -i image, the term is off (as upstream, clip_fft.py:268)')
+        else:
+            from aphantasia_amd import lpips as alpips
+            sync = alpips.load(h, w, a.vgg_weights, a.lpips_weights, device='cuda')
+            sync.set_target(F.interpolate(img_in, [h // 2, w // 2], mode='bicubic', align_corners=True).float())
+            if a.verbose is True: print(' sync: LPIPS (VGG-16) on %d x %d, arena %.0f MB' % (h // 2, w // 2, sync.workspace_bytes() / 2 ** 20))
+    pk['sync'] = sync
+    n_sync = max(a.steps // a.opt_step, 1)
     eng = Engine(leaf, h, w, model_clip, a.samples, targets, sim=a.sim, colors=a.colors, decay=a.decay, lr=lr0,
                  optimizer=a.optimizer, align=a.align, macro=a.macro, transform=trform_f, sharp=a.sharp, expand=a.expand, enforce=a.enforce, rng=a.rng,
                  rank=rank, world=world, comm=comm, aest=aest1, precise=a.precise, exact=a.exact, graph_allreduce=a.graph_allreduce or None, use_graph=not a.no_graph, **pk)
@@ -381,7 +403,7 @@ def main(argv=None):
         shift = None
         if a.noise > 0 and a.dwt is not True:
             shift = (a.noise * torch.rand(1, 1, h, w // 2 + 1, 1)).reshape(h, w // 2 + 1).cuda().contiguous()
-        e.step(lr=lr_cur, shift=shift)
+        e.step(lr=lr_cur, shift=shift, sync_weight=prog_sync(i, n_sync) * a.sync if sync is not None else None)
         if a.expand > 0:                                                                # clip_fft.py:276-280: prev_enc = out_enc.detach()
             for other in (eng, eng2):
                 if other is not None: other.set_prev_enc(e.enc)

@@ -296,6 +296,32 @@ int aph_text_set_weight(aph_text* text, const char* name, const float* h_data, s
  * Ids are clamped into [0, vocab_size) on the device, so no id reads out of bounds; callers should refuse them earlier. */
 int aph_text_forward(aph_text* text, const int32_t* d_tokens, int S, float* d_enc, void* stream);
 
+/* ---- LPIPS image term: clip_fft.py:219-222,268-270 (`--sync`), lpips.LPIPS(net='vgg') v0.1 with normalize=True --------------
+ * value = LPIPS(resize(rgb), resize(target)): both images [3,H,W] in [0,1] go through a bicubic resize (align_corners=True) to
+ * [H/2, W/2], the input scaling (2 t - 1, then (t - shift_c) / scale_c) and the VGG-16 feature stack (13 convolutions 3x3 + bias + ReLU,
+ * 2x2 max-pool before stages 2 .. 5); the five stage outputs are unit-normalised over channels, and the value is
+ * sum_l mean_hw sum_c lin_l[c] (n_l(x) - n_l(y))^2.  Convolutions on the f16 MFMA (f16 NHWC activations, fp32 accumulation), head and
+ * resize in fp32, spatial sums through fp64 partials; deterministic.  The network is frozen: the only gradient is the image's.
+ * widths[5]: channels of the five stages (VGG-16: 64, 128, 256, 512, 512), each a multiple of 16 up to 1024; H/2 and W/2 at least 16:
+ * else APH_ERR_UNSUPPORTED.  One arena holds weights, activations and the backward stream; it is sized at create and no later call
+ * allocates or waits for the device, so aph_lpips_value_grad can be captured into a graph. */
+typedef struct aph_lpips aph_lpips;
+int aph_lpips_create(const int* widths, int H, int W, aph_lpips** out);
+int aph_lpips_destroy(aph_lpips* lp);
+size_t aph_lpips_workspace_bytes(const aph_lpips* lp);
+/* one tensor (fp32 HOST data): features.N.weight [cout][cin][3][3] / features.N.bias [cout] with torchvision's vgg16 numbering
+ * (N = 0 2 5 7 10 12 14 17 19 21 24 26 28), linL.weight [C_L] for L = 0 .. 4.  Unknown key or wrong count: APH_ERR_ARG. */
+int aph_lpips_set_weight(aph_lpips* lp, const char* name, const float* h_data, size_t count);
+/* the constant image y: d_img f32 [3,h,w] (device), (h, w) = the full frame (resized here) or its half size (taken as is); computes and
+ * stores the normalised taps of y.  After every weight is set; again after a weight changes. */
+int aph_lpips_set_target(aph_lpips* lp, const float* d_img, int h, int w, void* stream);
+/* *d_loss (nullable) += *d_weight * value and d_rgb_grad [3,H,W] (nullable) += *d_weight * dvalue/drgb, d_rgb f32 [3,H,W].
+ * d_weight: ONE DEVICE float, read by the kernels at run time (a captured graph replays with whatever it holds then). */
+int aph_lpips_value_grad(aph_lpips* lp, const float* d_rgb, const float* d_weight, float* d_loss, float* d_rgb_grad, void* stream);
+/* the same on an image that already has the network's size: d_x, d_x_grad f32 [3,H/2,W/2] (what the reference's own call hands to
+ * lpips: its resize is done by the caller) */
+int aph_lpips_value_grad_half(aph_lpips* lp, const float* d_x, const float* d_weight, float* d_loss, float* d_x_grad, void* stream);
+
 /* ---- loss: aphantasia/utils.py:270-295 sim_func, assembled as at clip_fft.py:257-267 -------- */
 #define APH_SIM_COS 0   /* type None / 'cossim' */
 #define APH_SIM_MIX 1   /* 'mix' (default) */

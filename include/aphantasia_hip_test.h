@@ -151,6 +151,26 @@ int aph_gemm_ws_probe(const void* d_A, const void* d_Bt, int M, int N, int K, vo
  * d_trace: (workgroups x 8) uint64 or NULL. */
 int aph_gemm_rs_probe(const void* d_A, const void* d_Bt, int M, int N, int K, void* d_out, int kind, unsigned long long* d_trace, void* stream);
 
+/* ---- the LPIPS term's kernels alone (csrc/lpips_conv.h, lpips_ops.h).  Activations are f16 [H][W][C], channel-innermost. ----
+ * aph_lpips_pack_test: the weight packing of aph_lpips_set_weight.  h_w fp32 HOST [cout][cin][3][3] -> d_out f16:
+ *   dgrad 0: [9][cout][C], C = cin rounded up to 8;   dgrad 1: [9][N][cout], N = cin rounded up to 16, taps flipped.  out_elems = that size.
+ * aph_lpips_conv_test: one launch of the convolution kernel: d_in [H][W][C] (C % 8 == 0), d_wt packed [9][N][C] (N % 16 == 0), d_bias [N] or
+ *   NULL, relu 0 / 1, d_mask [H][W][N] or NULL (output zeroed where mask <= 0), d_out f16 [H][W][N] or NULL, d_out32 planar fp32 [n32][H][W]
+ *   or NULL; nf = output channels per workgroup / 16: 4, 2, 1, or 0 for the library's own rule (bit-identical either way).  The forward is (packed forward weights, bias, relu 1); the input gradient is (gradient as d_in, packed dgrad weights, mask).
+ * aph_lpips_pool_test: d_out (nullable) [H/2][W/2][C] = 2x2 floor max-pool of d_in; d_din (nullable) [H][W][C] = its backward of d_dpool,
+ *   argmax recomputed from d_in (first maximum in row-major window order).
+ * aph_lpips_head_test: features d_f against target features d_fy (f16 [P][C]): d_ny fp32 [P][C] = the normalised target, *d_value =
+ *   mean_p sum_c lin_c (n_c - ny_c)^2, d_hg (nullable) fp32 [P][C] = gcoef * d(sum_p ...)/df; d_partial: 512 doubles of scratch.
+ * aph_lpips_resize_test: adjoint 0: d_half [3][H/2][W/2] = bicubic resize (align_corners) of d_full [3][H][W]; adjoint 1: d_full += the
+ *   transpose applied to d_half. */
+int aph_lpips_pack_test(const float* h_w, int cout, int cin, int dgrad, void* d_out, size_t out_elems);
+int aph_lpips_conv_test(const void* d_in, int H, int W, int C, const void* d_wt, int N, const float* d_bias, int relu, const void* d_mask, void* d_out,
+                        float* d_out32, int n32, int nf, void* stream);
+int aph_lpips_pool_test(const void* d_in, int H, int W, int C, void* d_out, const void* d_dpool, void* d_din, void* stream);
+int aph_lpips_head_test(const void* d_f, const void* d_fy, const float* d_lin, int P, int C, float gcoef, float* d_ny, float* d_hg, double* d_partial,
+                        float* d_value, void* stream);
+int aph_lpips_resize_test(float* d_full, int H, int W, float* d_half, int adjoint, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
