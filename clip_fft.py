@@ -15,19 +15,16 @@ and the lpips package's vgg.pth), without them seeded synthetic weights are used
 """
 import argparse
 import os
-import shutil
 import sys
-import threading
-import queue
-import time
-import warnings
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+from aphantasia_amd import run                                                      # noqa: E402
+from aphantasia_amd.run import FrameWriter, check_samples, pick_transform           # noqa: E402,F401  (bench.py, tools/exp and the tests take them from here)
 
 clip_models = ['ViT-B/16', 'ViT-B/32', 'ViT-L/14', 'RN101', 'RN50x16', 'RN50x4', 'RN50']
 
@@ -137,101 +134,6 @@ def derate_samples(a):
     return s
 
 
-def pick_transform(name):
-    """-tf none | fast | custom | elastic (clip_fft.py:121-128 upstream) -> the Engine's `transform` argument"""
-    from aphantasia_amd import transforms
-    return {'fast': transforms.transforms_fast, 'custom': transforms.transforms_custom, 'elastic': transforms.transforms_elastic}.get(name) or transforms.normalize()
-
-
-def check_samples(n):
-    """upstream, `--samples 1` with the default `-tf fast` derates to int(1 * 0.95) = 0 cuts and dies in torch.cat([])
-    (clip_fft.py:169, utils.py:253); say so instead"""
-    if n < 1:
-        raise SystemExit(' --samples derates to %d cuts for this model / transform (clip_fft.py:125-169): nothing to optimise; '
-                         'raise --samples or use -tf none' % n)
-
-
-class FrameWriter:
-    """Background JPEG writers: the reference converts and encodes every frame synchronously inside the hot loop
-    (clip_fft.py:297-306, utils.py:94-100).  Here the loop only enqueues a device-side uint8 conversion and an async
-    copy into a pinned ring; a small thread pool waits for the copy event and encodes (PIL releases the GIL)."""
-    THREADS = 4        # (8 threads measured the same with-save rate: 153.6-154.0 vs 153.2 steps/s -- the encoders are not the limit)
-    RING = 16          # slots of (device uint8 buffer, pinned host buffer); a slot is reused only after its writer released it (below)
-
-    def __init__(self, h, w, switch_interval=None):
-        # switch_interval: optionally lower the interpreter's GIL switch interval (default 5 ms) for the encoder threads' sake.  Measured in
-        # round 6 (tools/exp/save_ab.py, profiles/r06_save_ab.txt): 158.7 / 158.6 / 158.7 steps/s at 5 / 0.5 / 0.1 ms against 163.8 without
-        # saving -- the 3 % the per-step frame costs is device work (the contrast-1.1 synthesis, the uint8 conversion, the copy) and the
-        # loop's own enqueue calls, not GIL hand-over; left at the interpreter's setting.
-        if switch_interval is not None and sys.getswitchinterval() > switch_interval:
-            sys.setswitchinterval(switch_interval)
-        self.q = queue.Queue(maxsize=8)
-        self.h, self.w = h, w
-        self.bufs = [torch.empty(h, w, 3, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
-        # device-side uint8 ring + a copy stream of its own: the conversion is ONE launch on the step's stream (aph_rgb_to_u8), the
-        # 2.7 MB device->host copy waits for it on the side stream, so the next step's launches do not queue behind the PCIe transfer
-        self.dev = None
-        self.copy_stream = None
-        self.n = 0
-        # slot discipline: `free[k]` is released by the worker AFTER imsave (a straggling encoder keeps its pinned buffer), and the copy
-        # event of the slot's previous use is waited for on the step's stream before aph_rgb_to_u8 rewrites the device buffer
-        self.free = [threading.Semaphore(1) for _ in range(self.RING)]
-        self.copy_ev = [None] * self.RING
-        self.ts = [threading.Thread(target=self._run, daemon=True) for _ in range(self.THREADS)]
-        for t in self.ts: t.start()
-
-    def _run(self):
-        from PIL import Image
-        while True:
-            item = self.q.get()
-            if item is None:
-                self.q.task_done()
-                return
-            buf, ev, fname, k = item
-            try:
-                ev.synchronize()
-                Image.fromarray(buf.numpy()).save(fname, quality=95)
-            finally:
-                self.free[k].release()
-                self.q.task_done()
-
-    def put(self, img, fname, gamma=1.0):
-        """img: device float32 [3,H,W] in [0,1]; same arithmetic as utils.checkout: clip(img ** gamma * 255, 0, 255).astype(uint8)"""
-        from aphantasia_amd import _ffi, ops
-        if self.dev is None:
-            self.dev = [torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=img.device) for _ in range(self.RING)]
-            self.copy_stream = torch.cuda.Stream(device=img.device)
-        k = self.n % self.RING
-        self.n += 1
-        buf, dbuf = self.bufs[k], self.dev[k]
-        img = img.contiguous()
-        self.free[k].acquire()                                        # the encoder that used this slot RING frames ago has written its file
-        if self.copy_ev[k] is not None:
-            torch.cuda.current_stream(img.device).wait_event(self.copy_ev[k])      # ... and its device->host copy has read dbuf
-        _ffi.lib().call('aph_rgb_to_u8', ops.ptr(img), self.h, self.w, float(gamma), ops.ptr(dbuf), ops._stream(img))
-        done = torch.cuda.Event(); done.record()                      # on the step's stream: the conversion has read `img`
-        self.copy_stream.wait_event(done)
-        with torch.cuda.stream(self.copy_stream):
-            buf.copy_(dbuf, non_blocking=True)
-            ev = torch.cuda.Event(); ev.record()
-        self.copy_ev[k] = ev
-        self.q.put((buf, ev, fname, k))
-
-    def drain(self):
-        """block until every frame handed to put() is on disk"""
-        self.q.join()
-
-    def close(self):
-        for _ in self.ts: self.q.put(None)
-        for t in self.ts: t.join()
-
-
-def _spawn_rank(local_rank, argv, world, port, run_id):
-    os.environ.update(RANK=str(local_rank), LOCAL_RANK=str(local_rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1',
-                      MASTER_PORT=str(port), APH_RUN_ID=run_id, HSA_ENABLE_IPC_MODE_LEGACY='0')
-    main(argv)
-
-
 def prog_sync(i, n):
     """the --sync term's decay over the run (clip_fft.py:269): (N - i) / N with N = steps // opt_step"""
     return (n - i) / n
@@ -239,34 +141,16 @@ def prog_sync(i, n):
 
 def main(argv=None):
     a = get_args(argv)
-    # ---- multi-GPU (the reference is single-GPU): the cuts are split over the ranks of one node, one process
-    # per GPU, ONE RCCL all-reduce of the parameter gradient per step (aph_allreduce_f32).  Either launched by torchrun (RANK /
-    # WORLD_SIZE / LOCAL_RANK in the environment) or spawned from here with --ranks N.
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    if a.ranks > 1 and 'RANK' not in os.environ:
-        from aphantasia_amd.comm import spawn_ranks
-        if a.seed is None:
-            argv = list(sys.argv[1:] if argv is None else argv) + ['--seed', str(int.from_bytes(os.urandom(3), 'little'))]    # every rank must draw the same crop tables
-        port = 20000 + int.from_bytes(os.urandom(2), 'little') % 20000
-        spawn_ranks(_spawn_rank, (list(sys.argv[1:] if argv is None else argv), a.ranks, port, 'r%d' % os.getpid()), a.ranks)
+    ranks = run.bootstrap_ranks(a, argv, main, 'r', verbose=False, no_save=True, save_pt=False)      # (--ranks N: the ranks were spawned and have run)
+    if ranks is None:
         return
-    comm = None
-    if world > 1:
-        if a.seed is None:
-            raise SystemExit(' multi-rank runs need --seed (every rank draws the same crop / augment tables and takes its share of the cuts)')
-        torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', rank)))
-        from aphantasia_amd import comm as acomm
-        comm = acomm.create(rank, world)
-        if rank != 0:
-            a.verbose, a.no_save, a.save_pt = False, True, False          # rank 0 reports and writes the frames
-    if a.seed is not None:
-        torch.manual_seed(a.seed)
-        np.random.seed(a.seed)
+    rank, world, comm = ranks
+    run.seed_all(a.seed)
     if not a.model.startswith('ViT'):
         raise SystemExit(' the MI355X path covers the ViT CLIP models (ViT-B/32, ViT-B/16, ViT-L/14); got %s' % a.model)
-    from aphantasia_amd import clip as aclip, transforms
+    from aphantasia_amd import clip as aclip
     from aphantasia_amd.image import to_valid_rgb, fft_image, dwt_image
-    from aphantasia_amd.utils import slice_imgs, sim_func, basename, img_list, img_read, txt_clean
+    from aphantasia_amd.utils import basename, txt_clean
     from aphantasia_amd.engine import Engine
 
     shape = [1, 3, *a.size]
@@ -284,29 +168,16 @@ def main(argv=None):
         lr0 = a.lrate
     sign = 1. if a.invert is True else -1.
 
-    with warnings.catch_warnings():
-        if a.clip_weights is None:
-            print(' !! no --clip-weights given: using seeded SYNTHETIC CLIP weights (timing / plumbing only)')
-            warnings.simplefilter('ignore')
-        model_clip, _ = aclip.load(a.model, weights=a.clip_weights)
-        a.modsize = model_clip.visual.input_resolution
-        if a.verbose is True: print(' using model', a.model)
-        a.samples = derate_samples(a)
-        check_samples(a.samples)
-        if a.dualmod is not None:
-            model_clip2, _ = aclip.load('ViT-B/16', weights=a.clip_weights2)
-            dualmod_nums = list(range(a.steps))[a.dualmod::a.dualmod]
-            print(' dual model every %d step' % a.dualmod)
+    model_clip, model_clip2 = run.load_models(a.model, a.clip_weights, 'ViT-B/16' if a.dualmod is not None else None, a.clip_weights2)
+    a.modsize = model_clip.visual.input_resolution
+    if a.verbose is True: print(' using model', a.model)
+    a.samples = derate_samples(a)
+    check_samples(a.samples)
+    if a.dualmod is not None:
+        print(' dual model every %d step' % a.dualmod)
 
     def enc_text(txt, model=model_clip):                                              # clip_fft.py:143-154
-        embs = []
-        for subtxt in txt.split('|'):
-            if ':' in subtxt:
-                [subtxt, wt] = subtxt.split(':')
-                wt = float(wt)
-            else: wt = 1.
-            embs.append([aclip.text_embedding(model, subtxt, bpe_vocab=a.bpe_vocab), wt])
-        return embs
+        return [(aclip.text_embedding(model, subtxt, bpe_vocab=a.bpe_vocab), wt) for subtxt, wt in run.split_prompt(txt)]
 
     trform_f = pick_transform(a.transform)
     out_name = []
@@ -329,16 +200,11 @@ def main(argv=None):
         if a.dualmod is not None: targets2 += [(e, -sign * w) for e, w in enc_text(a.in_txt0, model_clip2)]
     if a.in_img is not None and os.path.isfile(a.in_img):
         if a.verbose is True: print(' ref image:', basename(a.in_img))
-        img_in = torch.from_numpy(img_read(a.in_img) / 255.).unsqueeze(0).permute(0, 3, 1, 2).cuda().float()[:, :3]
-        with torch.no_grad():
-            in_sliced = slice_imgs([img_in], a.samples, a.modsize, transforms.normalize(), a.align,
-                                   patch=model_clip.visual.patch_size)[0]
-            targets.append((model_clip.encode_image(in_sliced).detach().clone(), sign * a.weight_img))   # per-cut pairs, clip_fft.py:216,267
-            if a.dualmod is not None:
-                targets2.append((model_clip2.encode_image(in_sliced).detach().clone(), sign * a.weight_img))
+        img_in, rows = run.image_target_rows(a.in_img, [m for m in (model_clip, model_clip2) if m is not None], a.samples, a.modsize, a.align)
+        for t, r in zip((targets, targets2), rows): t.append((r, sign * a.weight_img))                  # per-cut pairs, clip_fft.py:216,267
         out_name.append(basename(a.in_img).replace(' ', '_'))
     assert targets, ' Loss not defined, check the inputs'                              # clip_fft.py:286
-    aclip.release_text(model_clip, model_clip2 if a.dualmod is not None else None)     # the targets are built: the text arenas can go
+    aclip.release_text(model_clip, model_clip2)     # the targets are built: the text arenas can go
 
     if a.verbose is True: print(' samples:', a.samples)
     out_name = '-'.join(out_name)
@@ -346,23 +212,10 @@ def main(argv=None):
     tempdir = os.path.join(a.out_dir, out_name)
     os.makedirs(tempdir, exist_ok=True)
 
-    def load_aest(path):                                                              # utils.py:402-413 aesthetic_model()
-        if a.aest == 0:
-            return None
-        if path is None or not os.path.isfile(path):
-            raise SystemExit(' --aest needs the LAION linear head: pass its state dict with --aest-weights (upstream downloads '
-                             'sa_0_4_<model>_linear.pth from github.com/LAION-AI/aesthetic-predictor; there is no network here)')
-        sd = torch.load(path, map_location='cpu')
-        return (sd['weight'].float(), float(sd['bias'].reshape(-1)[0]), a.aest)
-
-    def check_aest(head, model, flag):                                                # utils.py:403: nf = 768 for ViT-L/14, 512 for ViT-B/*
-        if head is not None and head[0].numel() != model.visual.output_dim:
-            raise SystemExit(' %s: a head of %d inputs, but %s encodes into %d (sa_0_4_vit_l_14_linear.pth is the 768-wide one)'
-                             % (flag, head[0].numel(), model.name, model.visual.output_dim))
-    aest1 = load_aest(a.aest_weights)
-    aest2 = load_aest(a.aest_weights2) if a.dualmod is not None else None
-    check_aest(aest1, model_clip, '--aest-weights')
-    if a.dualmod is not None: check_aest(aest2, model_clip2, '--aest-weights2')
+    aest1 = run.load_aest(a.aest_weights, a.aest)
+    aest2 = run.load_aest(a.aest_weights2, a.aest) if a.dualmod is not None else None
+    run.check_aest(aest1, model_clip, '--aest-weights')
+    if a.dualmod is not None: run.check_aest(aest2, model_clip2, '--aest-weights2')
     h, w = a.size
     if a.dwt is True:
         pk = dict(param_kind='dwt', dwt=image_f.synth)
@@ -396,9 +249,9 @@ def main(argv=None):
     writer = None if a.no_save else FrameWriter(h, w)
     # empirical tone mapping of the saved frames (clip_fft.py:300-303): **1.3 with --sync, **(1 + sharp/2) with --sharp
     gamma = 1.3 if (a.sync > 0 and a.in_img is not None) else (1 + a.sharp / 2. if a.sharp != 0 else 1.0)
-    t0 = time.time()
+    prog = run.Progress(a.steps, 'step', a.verbose, world)
     for i in range(a.steps):
-        e = eng2 if (eng2 is not None and i in dualmod_nums) else eng
+        e = eng2 if run.is_dual_step(i, a.dualmod) else eng
         lr_cur = lr0 + (i / a.steps) * (lr1 - lr0) if a.prog is True else lr0      # clip_fft.py:288-291
         shift = None
         if a.noise > 0 and a.dwt is not True:
@@ -410,22 +263,14 @@ def main(argv=None):
         if i % a.opt_step == 0 and writer is not None:
             img = e.synthesize(a.contrast)                                              # clip_fft.py:298-299
             writer.put(img.reshape(3, h, w), os.path.join(tempdir, '%04d.jpg' % (i // a.opt_step)), gamma)
-        if (a.verbose or world > 1) and (i % 10 == 9 or i == a.steps - 1):
-            gl = e.global_loss()               # (a collective when world > 1: every rank takes part, rank 0 prints)
-            if a.verbose:
-                print(' step %d/%d  loss %.4f  %.1f steps/s' % (i + 1, a.steps, gl, (i + 1) / (time.time() - t0)), flush=True)
+        prog.tick(i, e)
     torch.cuda.synchronize()
     if writer is not None:
-        writer.close()
-        if shutil.which('ffmpeg'):
-            os.system('ffmpeg -v warning -y -i %s/\\%%04d.jpg "%s.mp4"' % (tempdir, os.path.join(a.out_dir, out_name)))
-        frames = img_list(tempdir)
-        if frames:
-            shutil.copy(frames[-1], os.path.join(a.out_dir, '%s-%d.jpg' % (out_name, a.steps)))
+        run.finish_frames(writer, tempdir, '%04d', os.path.join(a.out_dir, out_name), os.path.join(a.out_dir, '%s-%d.jpg' % (out_name, a.steps)))
     if a.save_pt is True:
         torch.save([p.detach().cpu() for p in params], '%s.pt' % os.path.join(a.out_dir, out_name))   # clip_fft.py:315 (list of tensors)
     if rank == 0:
-        print(' done: %d steps in %.1fs (%.1f steps/s)%s' % (a.steps, time.time() - t0, a.steps / (time.time() - t0), ' on %d ranks' % world if world > 1 else ''))
+        prog.done()
 
 
 if __name__ == '__main__':

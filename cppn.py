@@ -13,16 +13,14 @@ cppn.py:197's 0.11 derating, is the follow-up.)
 """
 import argparse
 import os
-import shutil
 import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+from aphantasia_amd import run          # noqa: E402
 
 clip_models = ['ViT-B/16', 'ViT-B/32', 'ViT-L/14', 'RN50', 'RN50x4', 'RN50x16', 'RN50x64', 'RN101']
 
@@ -105,13 +103,10 @@ def derate_samples(a):
 
 def main(argv=None):
     a = get_args(argv)
-    if a.seed is not None:
-        torch.manual_seed(a.seed)
-        np.random.seed(a.seed)
-    from clip_fft import FrameWriter, check_samples
+    run.seed_all(a.seed)
     from aphantasia_amd import clip as aclip, transforms
     from aphantasia_amd.cppn import cppn_image, export_data
-    from aphantasia_amd.utils import slice_imgs, basename, img_list, img_read, txt_clean
+    from aphantasia_amd.utils import basename, txt_clean
     from aphantasia_amd.engine import Engine
 
     resume = a.resume if a.resume is not None and os.path.isfile(a.resume) else None          # cppn.py:179
@@ -120,29 +115,14 @@ def main(argv=None):
     a.layers, a.nf, a.actfn = syn.layers, syn.nf, syn.actfn
     print(' .. %d vars, %d layers, %d nf, act %s' % (len(params), a.layers, a.nf, a.actfn))
 
-    with warnings.catch_warnings():
-        if a.clip_weights is None:
-            print(' !! no --clip-weights given: using seeded SYNTHETIC CLIP weights (timing / plumbing only)')
-            warnings.simplefilter('ignore')
-        model_clip, _ = aclip.load(a.model, weights=a.clip_weights)
-        a.modsize = model_clip.visual.input_resolution
-        a.samples = derate_samples(a)
-        check_samples(a.samples)
-        model_clip2 = None
-        if a.dualmod is not None:
-            model_clip2, _ = aclip.load('ViT-B/16', weights=a.clip_weights2)
-            dualmod_nums = list(range(a.steps))[a.dualmod::a.dualmod]
-            print(' dual model every %d step' % a.dualmod)
-
-    def load_aest(path):                                                              # utils.py:402-413 aesthetic_model()
-        if a.aest == 0:
-            return None
-        if path is None or not os.path.isfile(path):
-            raise SystemExit(' --aest needs the LAION linear head: pass its state dict with --aest-weights (upstream downloads it; there is no network here)')
-        sd = torch.load(path, map_location='cpu')
-        return (sd['weight'].float(), float(sd['bias'].reshape(-1)[0]), a.aest)
-    aest1 = load_aest(a.aest_weights)
-    aest2 = load_aest(a.aest_weights2) if a.dualmod is not None else None
+    model_clip, model_clip2 = run.load_models(a.model, a.clip_weights, 'ViT-B/16' if a.dualmod is not None else None, a.clip_weights2)
+    a.modsize = model_clip.visual.input_resolution
+    a.samples = derate_samples(a)
+    run.check_samples(a.samples)
+    if a.dualmod is not None:
+        print(' dual model every %d step' % a.dualmod)
+    aest1 = run.load_aest(a.aest_weights, a.aest)
+    aest2 = run.load_aest(a.aest_weights2, a.aest) if a.dualmod is not None else None
 
     trform_f = transforms.transforms_fast if a.transform is True else transforms.normalize()
     models = [model_clip] + ([model_clip2] if model_clip2 is not None else [])
@@ -157,10 +137,8 @@ def main(argv=None):
         for t, m in zip(targets, models): t.append((aclip.text_embedding(m, a.in_txt0, bpe_vocab=a.bpe_vocab), 0.5))
     if a.in_img is not None and os.path.isfile(a.in_img):
         print(' ref image:', basename(a.in_img))
-        img_in = torch.from_numpy(img_read(a.in_img) / 255.).unsqueeze(0).permute(0, 3, 1, 2).cuda().float()[:, :3]
-        with torch.no_grad():
-            in_sliced = slice_imgs([img_in], a.samples, a.modsize, transforms.normalize(), a.align, patch=model_clip.visual.patch_size)[0]
-            for t, m in zip(targets, models): t.append((m.encode_image(in_sliced).detach().clone(), -1.0))      # per-cut pairs
+        rows = run.image_target_rows(a.in_img, models, a.samples, a.modsize, a.align)[1]
+        for t, r in zip(targets, rows): t.append((r, -1.0))                                                     # per-cut pairs
         out_name.append(basename(a.in_img).replace(' ', '_'))
     if not targets[0]:
         raise SystemExit(' Loss not defined, check the inputs (-t, -t0, -i)')
@@ -182,27 +160,21 @@ def main(argv=None):
     if model_clip2 is not None:
         eng2 = Engine(image_f.flat, h, w, model_clip2, a.samples, targets[1], aest=aest2, state=eng.state(), **common)
 
-    writer = None if a.no_save else FrameWriter(h, w)
-    t0 = time.time()
+    writer = None if a.no_save else run.FrameWriter(h, w)
+    prog = run.Progress(a.steps, 'step', a.verbose)
     for i in range(a.steps):
-        e = eng2 if (eng2 is not None and i in dualmod_nums) else eng
+        e = eng2 if run.is_dual_step(i, a.dualmod) else eng
         e.step()
         if i % a.fstep == 0 and writer is not None:                                   # cppn.py:299-304
             fname = os.path.join(tempdir, '%04d' % (i // a.fstep))
             writer.put(e.synthesize().reshape(3, h, w), fname + '.jpg')
             export_data(image_f.state_dict(), fname)
-        if a.verbose and (i % 10 == 9 or i == a.steps - 1):
-            print(' step %d/%d  loss %.4f  %.1f steps/s' % (i + 1, a.steps, e.global_loss(), (i + 1) / (time.time() - t0)), flush=True)
+        prog.tick(i, e)
     torch.cuda.synchronize()
     if writer is not None:
-        writer.close()
         export_data(image_f.state_dict(), out_name)                                    # cppn.py:312 (the .npy; no shaders)
-        if shutil.which('ffmpeg'):
-            os.system('ffmpeg -v warning -y -i %s/\\%%04d.jpg "%s.mp4"' % (tempdir, out_name))
-        frames = img_list(tempdir)
-        if frames:
-            shutil.copy(frames[-1], out_name + '-%d.jpg' % a.steps)
-    print(' done: %d steps in %.1fs (%.1f steps/s)' % (a.steps, time.time() - t0, a.steps / (time.time() - t0)))
+        run.finish_frames(writer, tempdir, '%04d', out_name, out_name + '-%d.jpg' % a.steps)
+    prog.done()
 
 
 if __name__ == '__main__':

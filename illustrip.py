@@ -16,16 +16,14 @@ translation.  The flags exist and are refused with a message instead of being si
 """
 import argparse
 import os
-import shutil
 import sys
-import time
-import warnings
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+from aphantasia_amd import run          # noqa: E402
 
 
 def get_args(argv=None):
@@ -113,68 +111,38 @@ def check_supported(a):
         raise SystemExit(' --aest is not part of this path')
 
 
-def _spawn_rank(local_rank, argv, world, port, run_id):
-    os.environ.update(RANK=str(local_rank), LOCAL_RANK=str(local_rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1',
-                      MASTER_PORT=str(port), APH_RUN_ID=run_id, HSA_ENABLE_IPC_MODE_LEGACY='0')
-    main(argv)
-
-
 def main(argv=None):
     a = get_args(argv)
     # multi-GPU as clip_fft.py: every rank holds the same picture, draws the same crop tables (same seed) and takes its share of the
     # cuts; one RCCL all-reduce of the parameter gradient per step.  The per-frame warp / re-parameterisation is replicated.
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    if a.ranks > 1 and 'RANK' not in os.environ:
-        from aphantasia_amd.comm import spawn_ranks
-        args = list(sys.argv[1:] if argv is None else argv)
-        if a.seed is None:
-            args += ['--seed', str(int.from_bytes(os.urandom(3), 'little'))]
-        port = 20000 + int.from_bytes(os.urandom(2), 'little') % 20000
-        spawn_ranks(_spawn_rank, (args, a.ranks, port, 'i%d' % os.getpid()), a.ranks)
+    ranks = run.bootstrap_ranks(a, argv, main, 'i', verbose=False, no_save=True, depth_dir=None)      # rank 0 reports and writes the frames / depth maps
+    if ranks is None:
         return
-    comm = None
-    if world > 1:
-        if a.seed is None:
-            raise SystemExit(' multi-rank runs need --seed (every rank draws the same crop / augment tables and takes its share of the cuts)')
-        torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', rank)))
-        from aphantasia_amd import comm as acomm
-        comm = acomm.create(rank, world)
-        if rank != 0:
-            a.verbose, a.no_save, a.depth_dir = False, True, None            # rank 0 reports and writes the frames / depth maps
+    rank, world, comm = ranks
     check_supported(a)
     if a.in_txt is None and a.in_txt2 is None:
         raise SystemExit(' give a prompt with -t (a text file with several lines / topic interpolation is not part of this path)')
     for t in (a.in_txt, a.in_txt2, a.in_txt0):
         if t is not None and os.path.isfile(t):
             raise SystemExit(' text files (one prompt per line, interpolated) are not part of this path: pass the prompt itself')
-    if a.seed is not None:
-        torch.manual_seed(a.seed); np.random.seed(a.seed)
-    import clip_fft
-    from aphantasia_amd import clip as aclip, transforms
+    run.seed_all(a.seed)
+    from aphantasia_amd import clip as aclip
     from aphantasia_amd.engine import Engine
     from aphantasia_amd.illustrip_loop import FrameLoop
     from aphantasia_amd.utils import txt_clean
-    with warnings.catch_warnings():
-        if a.clip_weights is None:
-            print(' !! no --clip-weights given: using seeded SYNTHETIC CLIP weights (timing / plumbing only)')
-            warnings.simplefilter('ignore')
-        model = aclip.load(a.model, weights=a.clip_weights)[0]
-        model2 = aclip.load('ViT-B/16', weights=a.clip_weights2)[0] if a.dualmod is not None else None
+    model, model2 = run.load_models(a.model, a.clip_weights, 'ViT-B/16' if a.dualmod is not None else None, a.clip_weights2)
     S = derate_samples(a)
-    clip_fft.check_samples(S)
+    run.check_samples(S)
     h, w = a.size
 
     def targets_for(m):
         out = []
         for txt, sign in ((a.in_txt, -a.invert), (a.in_txt2, -1.0), (a.in_txt0, 1.0)):          # illustrip.py:442-450
             if txt is None: continue
-            for sub in txt.split('|'):
-                wt = 1.
-                if ':' in sub: sub, wt = sub.split(':')[0], float(sub.split(':')[1])
-                out.append((aclip.text_embedding(m, sub, bpe_vocab=a.bpe_vocab), sign * wt))
+            out += [(aclip.text_embedding(m, sub, bpe_vocab=a.bpe_vocab), sign * wt) for sub, wt in run.split_prompt(txt)]
         m.release_text()          # the targets are built: the text arena can go
         return out
-    trf = clip_fft.pick_transform(a.transform)
+    trf = run.pick_transform(a.transform)
     if a.gen == 'RGB':                                                                          # illustrip.py:270-272: pixel_image([1,3,*size], resume) -> randn * sd, sd = 1 (image.py:98-101)
         leaf = torch.randn(1, 3, h, w).cuda().contiguous()
         pk = dict(param_kind='pixel', rgb_priors=True, fixcontrast=a.fixcontrast, decay=1.0)
@@ -196,24 +164,19 @@ def main(argv=None):
     name = txt_clean(a.in_txt or a.in_txt2).lower()[:40] + '-%s' % a.gen
     tempdir = os.path.join(a.out_dir, name)
     os.makedirs(tempdir, exist_ok=True)
-    writer = None if a.no_save else clip_fft.FrameWriter(h, w)
-    t0 = time.time()
+    writer = None if a.no_save else run.FrameWriter(h, w)
+    prog = run.Progress(a.steps, 'frame', a.verbose, world)
     for num in range(a.steps):
         img = loop.frame(1 + a.scale, [0, a.shift], a.angle, a.shear, contrast=None if writer is None else a.contrast,     # illustrip.py:381-384 (anima off)
                          noise=a.noise if a.gen == 'FFT' else 0.0, consume_noise_draw=(a.gen != 'FFT' and a.noise > 0 and a.rng == 'reference'))
         if writer is not None:
             writer.put(img.reshape(3, h, w), os.path.join(tempdir, '%06d.jpg' % num), 1.0)
-        if (a.verbose or world > 1) and (num % 10 == 9 or num == a.steps - 1):
-            gl = eng.global_loss()             # (a collective when world > 1: every rank takes part, rank 0 prints)
-            if a.verbose:
-                print(' frame %d/%d  loss %.4f  %.1f frames/s' % (num + 1, a.steps, gl, (num + 1) / (time.time() - t0)), flush=True)
+        prog.tick(num, eng)
     torch.cuda.synchronize()
     if writer is not None:
-        writer.close()
-        if shutil.which('ffmpeg'):
-            os.system('ffmpeg -v warning -y -i %s/\\%%06d.jpg "%s.mp4"' % (tempdir, os.path.join(a.out_dir, name)))
+        run.finish_frames(writer, tempdir, '%06d', os.path.join(a.out_dir, name))
     if rank == 0:
-        print(' done: %d frames in %.1fs (%.1f frames/s)%s' % (a.steps, time.time() - t0, a.steps / (time.time() - t0), ' on %d ranks' % world if world > 1 else ''))
+        prog.done()
 
 
 if __name__ == '__main__':
