@@ -7,7 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libaphantasia_hip.so')
-SOURCES = ['api.hip', 'synth.hip', 'dwt.hip', 'sampler.hip', 'loss_adam.hip', 'vit.hip', 'text.hip', 'vit_test.hip', 'lpips.hip', 'lpips_test.hip', 'comm.hip', 'depthwarp.hip']
+SOURCES = ['api.hip', 'synth.hip', 'dwt.hip', 'sampler.hip', 'loss_adam.hip', 'vit.hip', 'text.hip', 'vit_test.hip', 'lpips.hip', 'lpips_test.hip', 'depth.hip', 'depth_net_test.hip', 'comm.hip',
+           'depthwarp.hip']
 
 
 def _stale():

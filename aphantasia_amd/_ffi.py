@@ -83,6 +83,19 @@ _PROTOTYPES = {
     'aph_lpips_pool_test': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aph_lpips_head_test': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'aph_lpips_resize_test': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'aph_depth_create': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    'aph_depth_destroy': (c_int, [c_void_p]),
+    'aph_depth_workspace_bytes': (c_size_t, [c_void_p]),
+    'aph_depth_set_weight': (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
+    'aph_depth_set_pos_embed': (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t]),
+    'aph_depth_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'aph_depth_attn_test': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'aph_depth_conv_test': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p]),
+    'aph_depth_gemm_test': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'aph_depth_convt_test': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'aph_depth_resize_test': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'aph_depth_gelu_gemm_test': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'aph_frame_affine': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_void_p, c_void_p]),
     'aph_patchify_f16': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'aph_patchify_f16_hilo': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

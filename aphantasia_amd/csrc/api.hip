@@ -40,11 +40,14 @@ int aph_version(void) { return 200; }
 const char* aph_last_error(void) { return g_err; }
 }
 
-// The interpreter build (tests/emu/build_emu.py) compiles a fixed list of units that has neither vit_test.hip nor text.hip nor the LPIPS units: it
-// takes the ViT's test and measurement entries, the text tower and the LPIPS term with its test entries from here.  The gfx950 build compiles both as units of their own (aphantasia_amd/_build.py).
+// The interpreter build (tests/emu/build_emu.py) compiles a fixed list of units that has neither vit_test.hip nor text.hip nor the LPIPS nor the
+// depth estimator's units: it takes the ViT's test and measurement entries, the text tower, the LPIPS term and the depth estimator with their
+// test entries from here.  The gfx950 build compiles them as units of their own (aphantasia_amd/_build.py).
 #ifdef APH_EMU
 #include "vit_test.hip"
 #include "text.hip"
 #include "lpips.hip"
 #include "lpips_test.hip"
+#include "depth.hip"
+#include "depth_net_test.hip"
 #endif

@@ -40,11 +40,25 @@ struct ConvArgs {
   const half_t* mask;                  // [H][W][N] or null: the output is zeroed where mask <= 0
   half_t* out;                         // [H][W][N] or null
   float* out32; int n32;               // planar [n32][H][W] (channels < n32) or null
+  // read by the X instantiation alone (conv3x3_kernel<NF, true>, the depth estimator's convolutions): blockIdx.z = the image of a batch
+  int relu_in = 0;                     // ReLU on the input as it is staged (the pre-activation of a residual unit)
+  const half_t* res = nullptr;         // [H][W][N] or null: added in fp32 after bias / ReLU, before the one rounding
+  const half_t* res2 = nullptr;        // a second such term
+  int batch = 1;                       // images; in, res, res2, out advance by H W C / H W N per image (mask, out32: not with a batch)
 };
 
-template <int NF>
+// X = false: the LPIPS term's kernel, exactly as it was.  X = true adds what the fields after n32 say, and nothing to the sums: the same
+// chunk-by-chunk, tap-by-tap accumulation.
+template <int NF, bool X = false>
 static __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
   constexpr int kNT = NF * 16;                                     // output channels per workgroup
+  if constexpr (X) {
+    const size_t bi = (size_t)blockIdx.z * a.H * a.W * a.C, bo = (size_t)blockIdx.z * a.H * a.W * a.N;
+    a.in += bi;
+    if (a.out) a.out += bo;
+    if (a.res) a.res += bo;
+    if (a.res2) a.res2 += bo;
+  }
   APH_DYN_SMEM(smem);
   half_t* sA = reinterpret_cast<half_t*>(smem);
   half_t* sB = sA + kLdsA;
@@ -68,6 +82,14 @@ static __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
       const int y = y0 + hy - 1, x = x0 + hx - 1, c = c0 + v * 8;
       uint4 val = make_uint4(0u, 0u, 0u, 0u);
       if (y >= 0 && y < a.H && x >= 0 && x < a.W && c < a.C) val = *reinterpret_cast<const uint4*>(a.in + ((size_t)y * a.W + x) * a.C + c);
+      if constexpr (X) {
+        if (a.relu_in) {
+          half8 h = *reinterpret_cast<const half8*>(&val);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) h[e] = h[e] > (half_t)0.f ? h[e] : (half_t)0.f;
+          val = *reinterpret_cast<const uint4*>(&h);
+        }
+      }
       *reinterpret_cast<uint4*>(sA + p * kPS + v * 8) = val;
     }
     for (int i = tid; i < 9 * kNT * 4; i += 256) {
@@ -115,6 +137,18 @@ static __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = (float)m[r] > 0.f ? v[r] : 0.f;
       }
+      if constexpr (X) {
+        if (a.res) {
+          const half4 q = *reinterpret_cast<const half4*>(a.res + pix * a.N + n);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] += (float)q[r];
+        }
+        if (a.res2) {
+          const half4 q = *reinterpret_cast<const half4*>(a.res2 + pix * a.N + n);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] += (float)q[r];
+        }
+      }
       if (a.out) {
         half4 h;
 #pragma unroll
@@ -130,22 +164,24 @@ static __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
   }
 }
 
-template <int NF>
+template <int NF, bool X = false>
 static inline void launch_conv_nf(const ConvArgs& a, unsigned tiles, hipStream_t st) {
-  APH_ALLOW_SMEM(conv3x3_kernel<NF>, conv_smem<NF>());
-  APH_LAUNCH(conv3x3_kernel<NF>, dim3(tiles, (unsigned)((a.N + NF * 16 - 1) / (NF * 16))), dim3(256), conv_smem<NF>(), st, a);
+  APH_ALLOW_SMEM((conv3x3_kernel<NF, X>), conv_smem<NF>());
+  APH_LAUNCH((conv3x3_kernel<NF, X>), dim3(tiles, (unsigned)((a.N + NF * 16 - 1) / (NF * 16)), X ? (unsigned)a.batch : 1u), dim3(256), conv_smem<NF>(), st, a);
 }
 // nf: 16-channel fragments per workgroup, 4 / 2 / 1; 0 = the rule: 4, halved while the channels fit in half of it or the grid has fewer
 // workgroups than the chip has CUs
+template <bool X = false>
 static inline void launch_conv(const ConvArgs& a, hipStream_t st, int nf = 0) {
   const unsigned tiles = (unsigned)(((a.W + kTW - 1) / kTW) * ((a.H + kTH - 1) / kTH));
   if (nf == 0) {
+    const unsigned images = X ? (unsigned)a.batch : 1u;
     nf = 4;
-    while (nf > 1 && (16 * (nf / 2) >= a.N || tiles * (unsigned)((a.N + 16 * nf - 1) / (16 * nf)) < (unsigned)kCUs)) nf >>= 1;
+    while (nf > 1 && (16 * (nf / 2) >= a.N || images * tiles * (unsigned)((a.N + 16 * nf - 1) / (16 * nf)) < (unsigned)kCUs)) nf >>= 1;
   }
-  if (nf >= 4) launch_conv_nf<4>(a, tiles, st);
-  else if (nf == 2) launch_conv_nf<2>(a, tiles, st);
-  else launch_conv_nf<1>(a, tiles, st);
+  if (nf >= 4) launch_conv_nf<4, X>(a, tiles, st);
+  else if (nf == 2) launch_conv_nf<2, X>(a, tiles, st);
+  else launch_conv_nf<1, X>(a, tiles, st);
 }
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }

@@ -2,10 +2,10 @@
 and meaning: `resize`, `grid_warp`, `depthwarp`, `InferDepthAny`) and of illustrip.py:115-128 `depth_transform`, on the HIP
 kernels of csrc/depthwarp.hip (C ABI: aph_triangle_blur, aph_resize_bicubic, aph_flip_w, aph_grid_warp).
 
-What is NOT here is the depth estimator: Depth-Anything-V2 (depth.py:20-32) is a third-party DINOv2 + DPT network whose
-weights are not part of either repository.  `depthwarp` takes it as the `infer_any` callable, as the reference does;
-`InferDepthAny` loads it through `transformers` from a LOCAL directory (there is no network here) and fails loudly when
-none is given."""
+The depth estimator, Depth-Anything-V2 (depth.py:20-32), is a third-party DINOv2 + DPT network whose weights are not part of
+either repository.  `depthwarp` takes it as the `infer_any` callable, as the reference does; `InferDepthAny` reads it from a
+LOCAL Hugging Face checkpoint directory (there is no network here) and fails loudly when none is given.  Its default backend
+runs the checkpoint through `transformers` on PyTorch; backend='hip' runs it on the kernels of csrc/depth.hip (depthnet.py)."""
 import os
 
 import torch
@@ -73,8 +73,11 @@ def depth_map(img, infer_any, res=518, lib=None):
     _, _, H, W = img.shape
     dim = estimator_size(H, W, res)
     image = resize(triangle_blur(img, 5, 2, mix=0.5, lib=lib), dim, lib=lib)
-    d1 = infer_any(image)
-    d2 = infer_any(flip_w(image, lib=lib))
+    if getattr(infer_any, 'batched', False):      # the hip backend: the image and its mirror as one batch of two
+        d1, d2 = infer_any(torch.cat([image, flip_w(image, lib=lib)], 0))
+    else:
+        d1 = infer_any(image)
+        d2 = infer_any(flip_w(image, lib=lib))
     depth = flip_w(d2.reshape(1, 1, *dim), mul=d1.reshape(1, 1, *dim), lib=lib)
     return resize(depth, (H, W), lib=lib)
 
@@ -103,21 +106,40 @@ def depth_transform(img_t, _deptha, depthX=0, scale=1., shift=[0, 0], colors=1, 
 
 class InferDepthAny:
     """depth.py:20-32.  `path`: a local Depth-Anything-V2 checkpoint directory in Hugging Face format (or the environment
-    variable APH_DEPTH_WEIGHTS); the estimator itself runs on PyTorch -- it is not part of the HIP path."""
+    variable APH_DEPTH_WEIGHTS).  backend 'torch' (the default): the transformers model on PyTorch, fp32 -- not part of the HIP path;
+    backend 'hip': the same checkpoint on the kernels of csrc/depth.hip (aphantasia_amd.depthnet.DepthAnythingHIP), normalisation and
+    min-max included, and `depth_map` sends the image and its mirror as one batch of two (`batched`)."""
 
-    def __init__(self, modtype='B', device=None, path=None):
+    def __init__(self, modtype='B', device=None, path=None, backend='torch', lib=None):
+        if backend not in ('torch', 'hip'):
+            raise ValueError("InferDepthAny: backend %r is neither 'torch' nor 'hip'" % (backend,))
         path = path or os.environ.get('APH_DEPTH_WEIGHTS')
         if not path or not os.path.isdir(path):
             raise RuntimeError('InferDepthAny: no local Depth-Anything-V2 checkpoint (pass path= or set APH_DEPTH_WEIGHTS); this image has '
                                'no network access and the weights are not part of the repository')
-        from transformers import AutoModelForDepthEstimation
         self.device = torch.device(device if device is not None else 'cuda')
+        self.backend = backend
+        self.batched = backend == 'hip'
+        if backend == 'hip':
+            from .depthnet import DepthAnythingHIP
+            self.net = DepthAnythingHIP.from_pretrained_dir(path, lib=lib)
+            return
+        from transformers import AutoModelForDepthEstimation
         self.model = AutoModelForDepthEstimation.from_pretrained(path).to(self.device).eval()
         self.mean = torch.tensor([0.485, 0.456, 0.406], device=self.device).view(1, 3, 1, 1)
         self.std = torch.tensor([0.229, 0.224, 0.225], device=self.device).view(1, 3, 1, 1)
 
+    @classmethod
+    def from_estimator(cls, net, lib=None):
+        """the hip backend around a DepthAnythingHIP that already exists (tests, benchmarks: no checkpoint directory)"""
+        self = cls.__new__(cls)
+        self.backend, self.batched, self.net, self.device = 'hip', True, net, None
+        return self
+
     @torch.no_grad()
     def __call__(self, image):
+        if self.backend == 'hip':      # [B,3,h,w] -> [B,1,1,h,w]: indexing (or unpacking) the batch gives the torch backend's [1,1,h,w] per image
+            return self.net(image).unsqueeze(1)
         image = (image - self.mean) / self.std
         depth = self.model(pixel_values=image).predicted_depth.unsqueeze(0)
         return (depth - depth.min()) / (depth.max() - depth.min())

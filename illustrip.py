@@ -8,9 +8,10 @@ Per frame: warp the current picture by the frame's motion (scale / shift / angle
 restart the optimiser, take --opt_step optimisation steps against the prompt(s), save the frame (aphantasia_amd/
 illustrip_loop.py).  Built on the fused HIP engine; multi-GPU as clip_fft.py (cuts split over ranks, one RCCL all-reduce).
 
--d / --depth runs the depth warp (depth/depth.py:41-84 on HIP kernels); its estimator, Depth-Anything-V2, is loaded by
-`transformers` from a LOCAL checkpoint directory (--depth_weights or APH_DEPTH_WEIGHTS; there is no network here) and is the one
-part of the frame that runs on stock PyTorch.
+-d / --depth runs the depth warp (depth/depth.py:41-84 on HIP kernels); its estimator, Depth-Anything-V2, is read from a LOCAL
+checkpoint directory (--depth_weights or APH_DEPTH_WEIGHTS; there is no network here).  --depth_backend torch (the default) runs
+it through `transformers` on stock PyTorch -- then the one part of the frame that does; --depth_backend hip runs the same
+checkpoint on the HIP kernels of csrc/depth.hip (aphantasia_amd/depthnet.py), the image and its mirror as one batch of two.
 Out of this path's scope: multi-line text files with topic interpolation, `latent_anima` motion curves (the motion here is the constant one of `--anima False`), --aest, LPIPS,
 translation.  The flags exist and are refused with a message instead of being silently ignored.
 """
@@ -53,6 +54,8 @@ def get_args(argv=None):
     p.add_argument('--depth_model', default='b', help='Depth Anything model: large, base or small')
     p.add_argument('--depth_dir', default=None, help='Directory to save depth, if not None')
     p.add_argument('--depth_weights', default=None, help='local Depth-Anything-V2 checkpoint directory (HF format); or APH_DEPTH_WEIGHTS')
+    p.add_argument('--depth_backend', default='torch', choices=['torch', 'hip'],
+                   help='the depth estimator: transformers on PyTorch (default), or the HIP kernels of csrc/depth.hip on the same checkpoint')
     p.add_argument('-a', '--align', default='overscan', choices=['central', 'uniform', 'overscan', 'overmax'])
     p.add_argument('-tf', '--transform', default='fast', choices=['none', 'fast', 'custom', 'elastic'])
     p.add_argument('-opt', '--optimizer', default='adam_custom', choices=['adam', 'adam_custom', 'adamw', 'adamw_custom'])
@@ -156,7 +159,7 @@ def main(argv=None):
     depth_fn = None
     if a.depth > 0:
         from aphantasia_amd.depthwarp import InferDepthAny
-        depth_fn = InferDepthAny(a.depth_model, path=a.depth_weights)          # raises without a local checkpoint
+        depth_fn = InferDepthAny(a.depth_model, path=a.depth_weights, backend=a.depth_backend)          # raises without a local checkpoint
         if a.depth_dir is not None:
             os.makedirs(a.depth_dir, exist_ok=True)
     loop = FrameLoop(eng, gen=a.gen, opt_step=a.opt_step, smooth=a.smooth, engine2=eng2, dualmod=a.dualmod, depth=a.depth, depth_fn=depth_fn,

@@ -322,6 +322,28 @@ int aph_lpips_value_grad(aph_lpips* lp, const float* d_rgb, const float* d_weigh
  * lpips: its resize is done by the caller) */
 int aph_lpips_value_grad_half(aph_lpips* lp, const float* d_x, const float* d_weight, float* d_loss, float* d_x_grad, void* stream);
 
+/* ---- depth estimator: depth/depth.py:20-32, Depth-Anything-V2 (DINOv2 S / B / L + DPT neck and head) behind `illustrip.py -d` ----------
+ * Inference of transformers' DepthAnythingForDepthEstimation (relative depth): f16 MFMA GEMMs, attention and convolutions with fp32
+ * accumulation, an fp32 residual stream.  d_img f32 [B,3,h,w] in (0,1) (the ImageNet normalisation is part of the first kernel), h and w
+ * multiples of 14 up to max_h / max_w, B up to max_batch -> d_depth f32 [B,1,h,w]; normalise != 0: (d - min) / (max - min) per image, as
+ * InferDepthAny.__call__ does.  hidden = 64 * heads, a multiple of 128 up to 1024; out_indices[4]: the tapped layers (1-based, non-decreasing);
+ * neck_sizes[4] multiples of 16, fusion a multiple of 32, head_hidden a multiple of 16; swiglu != 0 (the giant encoder): APH_ERR_UNSUPPORTED.
+ * One arena holds weights and the activations of max_batch images of max_h x max_w; aph_depth_forward allocates nothing.
+ * aph_depth_set_weight: one tensor (fp32 HOST data) under its name in the Hugging Face state dict (backbone.embeddings.cls_token, ...
+ * head.conv3.bias); position_embeddings and mask_token are not taken.  Unknown name or wrong count: APH_ERR_ARG.
+ * aph_depth_set_pos_embed: the position rows [1 + gh gw][hidden] (fp32 HOST) for images of (14 gh) x (14 gw): row 0 the class position, the
+ * rest the checkpoint's 37 x 37 grid interpolated the way transformers does (bicubic, align_corners = False) -- set-up, done by the caller
+ * once per size (aphantasia_amd/depthnet.py).  aph_depth_forward refuses an image whose grid is not the one last set, names the first weight
+ * that was never set, and refuses h / w that are no multiple of 14 or exceed max_h / max_w and B above max_batch (APH_ERR_ARG). */
+typedef struct aph_depth aph_depth;
+int aph_depth_create(int hidden, int layers, int heads, int swiglu, const int* out_indices, const int* neck_sizes, int fusion, int head_hidden, int max_h,
+                     int max_w, int max_batch, aph_depth** out);
+int aph_depth_destroy(aph_depth* dn);
+size_t aph_depth_workspace_bytes(const aph_depth* dn);
+int aph_depth_set_weight(aph_depth* dn, const char* name, const float* h_data, size_t count);
+int aph_depth_set_pos_embed(aph_depth* dn, int gh, int gw, const float* h_rows, size_t count);
+int aph_depth_forward(aph_depth* dn, const float* d_img, int B, int h, int w, int normalise, float* d_depth, void* stream);
+
 /* ---- loss: aphantasia/utils.py:270-295 sim_func, assembled as at clip_fft.py:257-267 -------- */
 #define APH_SIM_COS 0   /* type None / 'cossim' */
 #define APH_SIM_MIX 1   /* 'mix' (default) */

@@ -171,6 +171,26 @@ int aph_lpips_head_test(const void* d_f, const void* d_fy, const float* d_lin, i
                         float* d_value, void* stream);
 int aph_lpips_resize_test(float* d_full, int H, int W, float* d_half, int adjoint, void* stream);
 
+/* ---- the depth estimator's kernels alone (csrc/depth_kernels.h, the batched / residual instantiation of lpips_conv.h, depth_epi.h's erf-GELU
+ * epilogue).  Activations are f16, channel-innermost.
+ * aph_depth_attn_test: d_att [B T][64 heads] = softmax(Q K^T / 8) V per (image, head) from d_qkv [B T][3 x 64 heads] (Q | K | V), any T >= 1.
+ * aph_depth_conv_test: 3 x 3 pad 1 convolution of `batch` maps d_in [batch][H][W][C] with d_wt packed [9][N][C] (aph_lpips_pack_test):
+ *   out = f16(relu?(conv(relu_in ? max(in, 0) : in) + bias) + res + res2) (d_bias, d_res, d_res2 [batch][H][W][N] nullable); stride 2: the
+ *   stride-1 result goes to d_tmp [batch][H][W][N] and its even rows / columns to d_out [batch][(H+1)/2][(W+1)/2][N].
+ * aph_depth_gemm_test: d_out [M][N] = d_a [M][lda] x d_bt [N][K]^T + d_bias (nullable), N % 16 == 0, K % 8 == 0: the neck's 1 x 1 convolution.
+ * aph_depth_convt_test: ConvTranspose2d with kernel = stride = k (1 .. 4): h_w fp32 HOST [cin][cout][k][k], d_wpack = k k cout cin f16 of
+ *   scratch, d_in [B][gh][gw][cin] -> d_out [B][gh k][gw k][cout].
+ * aph_depth_resize_test: bilinear, align_corners = True, d_in [B][h][w][C] -> d_out [B][H][W][C] (C % 8 == 0).
+ * aph_depth_gelu_gemm_test: d_out [M][N] = gelu_erf(d_a [M][K] x d_bt [N][K]^T + d_bias) through launch_gemm (N % 128 == 0, K % 64 == 0). */
+int aph_depth_attn_test(const void* d_qkv, void* d_att, int B, int T, int heads, void* stream);
+int aph_depth_conv_test(const void* d_in, int H, int W, int C, const void* d_wt, int N, const float* d_bias, int relu, int relu_in, const void* d_res,
+                        const void* d_res2, int batch, int stride, void* d_tmp, void* d_out, void* stream);
+int aph_depth_gemm_test(const void* d_a, int lda, const void* d_bt, int M, int N, int K, const float* d_bias, void* d_out, void* stream);
+int aph_depth_convt_test(const void* d_in, int B, int gh, int gw, int cin, const float* h_w, int cout, int k, const float* d_bias, void* d_wpack, void* d_out,
+                         void* stream);
+int aph_depth_resize_test(const void* d_in, int B, int h, int w, int C, void* d_out, int H, int W, void* stream);
+int aph_depth_gelu_gemm_test(const void* d_a, const void* d_bt, int M, int N, int K, const float* d_bias, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
